@@ -11,7 +11,14 @@ Weights: seeded synthetic (xavier convs, randomised BN; no checkpoints travel) â
 recipe as the committed golden fixture tests/golden/model_r18_c128_b1_480x640.npz, so the
 parity leg compares the benchmarked kernels against the reference's own outputs.
 
-Extra keys next to the contract's (all measured in this run, on rank 0):
+A plain run sets up, warms up, times --steps steps and prints the result line (metric, value,
+ms_per_step, ...); nothing else runs. --dump-outputs DIR then also writes what the last timed step
+computed (dump_arrays) as DIR/<name>.npy, for comparing two builds output for output: the inputs
+and weights are seeded, so they are the same from run to run.
+
+--full adds the legs below as extra keys next to the contract's (all measured in this run, on
+rank 0, after the timed steps):
+  eager_value      frames/s of the same step launched eagerly (the timed step is a hipGraph replay)
   roofline         dominant conv kernel: per-launch HIP events on the launch stream
   decode_roofline  the decode kernels' achieved HBM GB/s (algorithmic bytes / event time)
   parity           the timed precision's detections on the golden frame (inside a B-frame
@@ -28,7 +35,7 @@ Extra keys next to the contract's (all measured in this run, on rank 0):
   node_b1          the ROS node's per-frame call (centernet_node.py:90-116): CenterpointDLA34
                    model(img) -> decode_keypoints at B=1, fp32 and fp16, graph cache on / off
 
-Launch:  python bench.py [--gpus 1] [--steps 20] [--warmup 5]
+Launch:  python bench.py [--gpus 1] [--steps 20] [--warmup 5] [--dump-outputs DIR] [--full]
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 Rank 0 prints one JSON line. Any TV_* environment knob (kernel-choice overrides, an
 alternative library) makes the bench refuse to run unless --allow-env-knobs is given, and
@@ -167,6 +174,55 @@ def timed(fn, steps, warmup, world=1, device=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     return elapsed
+
+
+DUMP_SAMPLE = 1 << 19  # elements kept of an output larger than this (2 MB as float32)
+
+
+def sampled(t, seed, valid=None):
+    """`t` as a float32 host array; of a tensor with more than DUMP_SAMPLE elements, the elements
+    at DUMP_SAMPLE fixed indices of its flattened (logical order) form (seeded, so the same in every
+    run and build). `valid` (a bool tensor broadcastable to t's shape) zeroes the elements the step
+    leaves unwritten."""
+    ok = None if valid is None else valid.to(t.device).expand(t.shape)
+    if t.numel() > DUMP_SAMPLE:
+        idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed))
+        idx = idx.sort().values.to(t.device)
+        t = t.reshape(-1)[idx]
+        ok = None if ok is None else ok.reshape(-1)[idx]
+    t = t.float()
+    if ok is not None:
+        t = torch.where(ok, t, torch.zeros_like(t))
+    return t.cpu().numpy()
+
+
+def dump_arrays(path, arrays):
+    """--dump-outputs: one float32 <name>.npy per output of the last timed step."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def centernet_outputs(pipe, gather):
+    """What a caller of the timed step receives, as the last step left it: the host records
+    [frames, K, 10] and counts [frames] (every rank's frames after the all-gather; rows past a
+    frame's count are unwritten and dumped as 0, as are the columns of fields this model does not
+    have, which the decoder fills with NaN: depth without a depth head, the keypoint decode's two
+    aux columns), and a fixed sample of this rank's head tensors the records were decoded from."""
+    torch.cuda.synchronize()
+    if gather is not None:
+        rec, cnt = gather.unpack(pipe.host_gathered)
+    else:
+        rec, cnt = pipe.host, pipe.host_counts
+    rec, cnt = rec.clone(), cnt.clone()
+    rec[:, :, [8, 9] + ([6] if pipe.pred.depth is None else [])] = 0.0
+    rows = torch.arange(rec.shape[1])[None, :, None] < cnt[:, None, None]
+    out = {"records": sampled(rec, 11, rows), "counts": cnt.float().numpy()}
+    for i, f in enumerate(sorted(pipe.pred.__dataclass_fields__)):
+        t = getattr(pipe.pred, f)
+        if t is not None:
+            out["head_" + f] = sampled(t, 100 + i)
+    return out
 
 
 def load_traffic(kernel, batch, precision, model="r18"):
@@ -660,6 +716,32 @@ def run_yolact(args, world, rank, device):
         dist.destroy_process_group()  # the legs below are rank 0's alone (no collective)
         if rank != 0:
             return
+    peak = PEAK_TFLOPS[args.precision]
+    line = {
+        "metric": YOLACT_METRIC, "value": round(value, 2), "unit": "frames/sec", "n_gpus": world, "ranks": ranks,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.precision,
+        "data": "synthetic",
+        "config": {"workload": f"YOLACT 550x550: Masknet protonet (F={F}, k={k}) on fpn[0] 69x69 -> protos "
+                               f"276x276, box_decode of {A} anchors, fast NMS (top_k {top_k}, IoU 0.5, conf 0.05) "
+                               f"per frame, assemble_mask of the kept detections; batch={B}/GPU",
+                   "global_batch": B * world, "parallelism": f"dp{world}"},
+        "e2e_tflops": round(value * flops_frame / 1e12, 2),
+        "e2e_frac_of_peak": round(value * flops_frame / 1e12 / peak, 4),
+    }
+    if args.dump_outputs:
+        # the last timed step's outputs: prototypes, boxes, kept anchors per frame (rows past a
+        # frame's count are unwritten: dumped as 0), their masks, counts
+        torch.cuda.synchronize()
+        cnt = bnms.counts
+        rows = torch.arange(bnms.K, device=device)[None, :] < cnt[:, None]
+        dump_arrays(args.dump_outputs, {
+            "prototypes": sampled(pview, 21), "box": sampled(box_out["box"], 22),
+            "det": sampled(bnms.det, 23, rows), "counts": cnt.float().cpu().numpy(),
+            "masks": sampled(masks, 24, rows[:, :, None, None])})
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        return
 
     # dominant protonet kernel (per-launch HIP events) and the mask kernel's HBM rate
     prof = eng.profile(x, proto)
@@ -671,7 +753,6 @@ def run_yolact(args, world, rank, device):
             kk[1] += ms
             kk[2] += fl
     name, (n, ms, fl) = max(kern.items(), key=lambda kv: kv[1][1])
-    peak = PEAK_TFLOPS[args.precision]
     # in situ (as conv_roofline): the dominant kernel's launches timed inside the forward as the
     # timed region runs it (concurrent slices); the serialised whole-batch profile above is *_isolated
     # the slices' own launches (their workspaces' kernel choice may differ from the whole batch's)
@@ -748,20 +829,8 @@ def run_yolact(args, world, rank, device):
                "sample": f"{nfr} single frames (B=1): fp32 protonet + box_decode + nms + assemble_mask in {el:.1f}s; "
                          f"oracle/ PyTorch-CPU restatement, bit-identical to the reference on CPU"}
     if rank == 0:
-        line = {
-            "metric": YOLACT_METRIC, "value": round(value, 2), "unit": "frames/sec", "n_gpus": world, "ranks": ranks,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.precision,
-            "data": "synthetic",
-            "config": {"workload": f"YOLACT 550x550: Masknet protonet (F={F}, k={k}) on fpn[0] 69x69 -> protos "
-                                   f"276x276, box_decode of {A} anchors, fast NMS (top_k {top_k}, IoU 0.5, conf 0.05) "
-                                   f"per frame, assemble_mask of the kept detections; batch={B}/GPU",
-                       "global_batch": B * world, "parallelism": f"dp{world}"},
-            "e2e_tflops": round(value * flops_frame / 1e12, 2),
-            "e2e_frac_of_peak": round(value * flops_frame / 1e12 / peak, 4),
-            "roofline": roof, "mask_roofline": mask_roof, "nms_ms": round(best_nms, 4),
-            "detections_per_frame": round(kept / B, 2), "parity": parity, "cpu_baseline": cpu,
-        }
+        line.update({"roofline": roof, "mask_roofline": mask_roof, "nms_ms": round(best_nms, 4),
+                     "detections_per_frame": round(kept / B, 2), "parity": parity, "cpu_baseline": cpu})
         print(json.dumps(line), flush=True)
 
 
@@ -866,6 +935,11 @@ def main():
     ap.add_argument("--precision", default="fp16", choices=["fp16", "bf16", "fp32"])
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--thr", type=float, default=0.3)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the other legs (eager launch, rooflines, parity, fp32, "
+                         "B=1 latency, host feed, API, node, CPU baseline); the --no-* options trim them")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-b1", action="store_true")
@@ -889,6 +963,8 @@ def main():
 
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))  # before any GPU call: the ranks are children
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -927,7 +1003,9 @@ def main():
     elapsed = timed(step, args.steps, args.warmup, world, device)
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
-    if not args.eager:  # the same step launched eagerly, for comparison (same buffers)
+    if args.dump_outputs and rank == 0:  # before any other leg touches the step's buffers
+        dump_arrays(args.dump_outputs, centernet_outputs(pipe, gather))
+    if args.full and not args.eager:  # the same step launched eagerly, for comparison (same buffers)
         el_e = timed(lambda: pipe.step(frames, gather), args.steps, 2, world, device)
         eager_value = round(world * B * args.steps / el_e, 2)
     gathered = gather.world * gather.b_local if gather is not None else B
@@ -936,10 +1014,30 @@ def main():
         dist.destroy_process_group()  # the legs below are rank 0's alone (no collective)
         if rank != 0:
             return
+    flops_frame = pipe.eng.geom["flops_per_frame"]
+    workload = (f"CenterNet-R18 (Centernet+DLABackbone [2]*5/[128]*6, ds 2, heads [4,2,2]) " if args.model == "r18"
+                else "CenterpointDLA34 (DLA-34 + DLAUp/IDAUp with DCNv2, heads [4,4,8,2,2]) ")
+    line = {
+        "metric": METRIC if args.model == "r18" else METRIC.replace("CenterNet-R18", "CenterpointDLA34"),
+        "value": round(value, 2), "unit": "frames/sec", "n_gpus": world, "ranks": ranks,
+        "gathered_frames_per_step": gathered, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
+        "config": {"workload": workload + f"640x480 u8 frames, batch={B}/GPU, forward + decode(K={K}, thr={args.thr})",
+                   "global_batch": B * world, "parallelism": f"dp{world} (frame-sharded, RCCL all-gather of "
+                                                              f"detections)" if world > 1 else "dp1"},
+        "e2e_tflops": round(value * flops_frame / 1e12, 2),
+        "e2e_frac_of_peak": round(value * flops_frame / 1e12 / PEAK_TFLOPS[args.precision], 4),
+        "launch": launch,
+    }
+    if knobs:
+        line["env_knobs"] = knobs
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        return
 
     # roofline of the dominant kernel (separate pass with per-launch events)
     roof = conv_roofline(pipe, frames, args.precision, model=args.model)
-    flops_frame = pipe.eng.geom["flops_per_frame"]
     extras = {}
     if rank == 0 and not args.no_extras:
         extras["decode_roofline"] = decode_roofline(pipe)
@@ -970,25 +1068,8 @@ def main():
         cpu = cpu_baseline({k: v.detach().cpu() for k, v in sd.items()}, args.cpu_seconds, K, args.thr, args.model)
 
     if rank == 0:
-        workload = (f"CenterNet-R18 (Centernet+DLABackbone [2]*5/[128]*6, ds 2, heads [4,2,2]) " if args.model == "r18"
-                    else "CenterpointDLA34 (DLA-34 + DLAUp/IDAUp with DCNv2, heads [4,4,8,2,2]) ")
-        line = {
-            "metric": METRIC if args.model == "r18" else METRIC.replace("CenterNet-R18", "CenterpointDLA34"),
-            "value": round(value, 2), "unit": "frames/sec", "n_gpus": world, "ranks": ranks,
-            "gathered_frames_per_step": gathered, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
-            "config": {"workload": workload + f"640x480 u8 frames, batch={B}/GPU, forward + decode(K={K}, thr={args.thr})",
-                       "global_batch": B * world, "parallelism": f"dp{world} (frame-sharded, RCCL all-gather of "
-                                                                  f"detections)" if world > 1 else "dp1"},
-            "e2e_tflops": round(value * flops_frame / 1e12, 2),
-            "e2e_frac_of_peak": round(value * flops_frame / 1e12 / PEAK_TFLOPS[args.precision], 4),
-            "launch": launch, "eager_value": eager_value,
-            "roofline": roof, "latency_b1": b1, "cpu_baseline": cpu,
-        }
+        line.update({"eager_value": eager_value, "roofline": roof, "latency_b1": b1, "cpu_baseline": cpu})
         line.update(extras)
-        if knobs:
-            line["env_knobs"] = knobs
         print(json.dumps(line), flush=True)
 
 

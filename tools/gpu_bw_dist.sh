@@ -9,5 +9,5 @@ timeout -k 10 120 tools/micro/wr_pattern > $O/wr_pattern.txt 2>&1; rc=$?; echo "
 if [ $rc -ne 0 ]; then exit $rc; fi
 timeout -k 10 120 tools/micro/rw_pattern > $O/rw_pattern.txt 2>&1; rc=$?; echo "rw rc=$rc"; cat $O/rw_pattern.txt
 if [ $rc -ne 0 ]; then exit $rc; fi
-timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_dist1.log 2>&1; rc=$?; echo "dist bench rc=$rc"
+timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_dist1.log 2>&1; rc=$?; echo "dist bench rc=$rc"
 tail -1 $O/bench_dist1.log | cut -c1-600

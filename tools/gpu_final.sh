@@ -17,15 +17,15 @@ step() {
 step tests 600 python -u -m pytest -x -q --timeout 120 --timeout-method thread tests -m gpu
 grep -E "passed|failed|FAILED" $O/tests.log | tail -3
 step smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
-BENCH_PROFILE_OUT=$O/ops_r18.json step bench_r18 500 python bench.py
+BENCH_PROFILE_OUT=$O/ops_r18.json step bench_r18 500 python bench.py --full
 tail -1 $O/bench_r18.log | cut -c1-400
 for m in dla34 yolact; do
-  BENCH_PROFILE_OUT=$O/ops_$m.json step bench_$m 300 python bench.py --model $m --cpu-seconds 10
+  BENCH_PROFILE_OUT=$O/ops_$m.json step bench_$m 300 python bench.py --full --model $m --cpu-seconds 10
   tail -1 $O/bench_$m.log | cut -c1-300
 done
-step prof_r18 300 rocprofv3 --kernel-trace --stats -d $O/prof -o r18 --output-format csv -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-b1 --no-extras
-step prof_dla34 300 rocprofv3 --kernel-trace --stats -d $O/prof -o dla34 --output-format csv -- python bench.py --model dla34 --steps 10 --warmup 3 --no-cpu-baseline --no-b1 --no-extras
-step prof_yolact 300 rocprofv3 --kernel-trace --stats -d $O/prof -o yolact --output-format csv -- python bench.py --model yolact --steps 5 --warmup 2 --no-cpu-baseline --no-extras
+step prof_r18 300 rocprofv3 --kernel-trace --stats -d $O/prof -o r18 --output-format csv -- python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-b1 --no-extras
+step prof_dla34 300 rocprofv3 --kernel-trace --stats -d $O/prof -o dla34 --output-format csv -- python bench.py --full --model dla34 --steps 10 --warmup 3 --no-cpu-baseline --no-b1 --no-extras
+step prof_yolact 300 rocprofv3 --kernel-trace --stats -d $O/prof -o yolact --output-format csv -- python bench.py --full --model yolact --steps 5 --warmup 2 --no-cpu-baseline --no-extras
 for m in r18 dla34 yolact; do
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 120 rocprofv3 --pmc $c -d $O/pmc/$m -o $c --output-format csv -- python tools/prof_forward.py --iters 1 --model $m > $O/pmc/${m}_$c.log 2>&1

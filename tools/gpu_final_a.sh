@@ -17,9 +17,9 @@ step() {
 step tests 600 python -u -m pytest -x -q --timeout 120 --timeout-method thread tests -m gpu
 grep -E "passed|failed|FAILED" $O/tests.log | tail -3
 step smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
-BENCH_PROFILE_OUT=$O/ops_r18.json step bench_r18 500 python bench.py
+BENCH_PROFILE_OUT=$O/ops_r18.json step bench_r18 500 python bench.py --full
 tail -1 $O/bench_r18.log | cut -c1-400
 for m in dla34 yolact; do
-  BENCH_PROFILE_OUT=$O/ops_$m.json step bench_$m 300 python bench.py --model $m --cpu-seconds 10
+  BENCH_PROFILE_OUT=$O/ops_$m.json step bench_$m 300 python bench.py --full --model $m --cpu-seconds 10
   tail -1 $O/bench_$m.log | cut -c1-300
 done

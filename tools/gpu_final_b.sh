@@ -14,9 +14,9 @@ step() {
   if [ $rc -ge 124 ] || [ $rc -eq 134 ] || [ $rc -eq 139 ]; then echo "STOP after $name"; tail -30 $O/$name.log; exit $rc; fi
   return 0
 }
-step prof_r18 300 rocprofv3 --kernel-trace --stats -d $O/prof -o r18 --output-format csv -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-b1 --no-extras
-step prof_dla34 300 rocprofv3 --kernel-trace --stats -d $O/prof -o dla34 --output-format csv -- python bench.py --model dla34 --steps 10 --warmup 3 --no-cpu-baseline --no-b1 --no-extras
-step prof_yolact 300 rocprofv3 --kernel-trace --stats -d $O/prof -o yolact --output-format csv -- python bench.py --model yolact --steps 5 --warmup 2 --no-cpu-baseline --no-extras
+step prof_r18 300 rocprofv3 --kernel-trace --stats -d $O/prof -o r18 --output-format csv -- python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-b1 --no-extras
+step prof_dla34 300 rocprofv3 --kernel-trace --stats -d $O/prof -o dla34 --output-format csv -- python bench.py --full --model dla34 --steps 10 --warmup 3 --no-cpu-baseline --no-b1 --no-extras
+step prof_yolact 300 rocprofv3 --kernel-trace --stats -d $O/prof -o yolact --output-format csv -- python bench.py --full --model yolact --steps 5 --warmup 2 --no-cpu-baseline --no-extras
 for m in r18 dla34 yolact; do
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 120 rocprofv3 --pmc $c -d $O/pmc/$m -o $c --output-format csv -- python tools/prof_forward.py --iters 1 --model $m > $O/pmc/${m}_$c.log 2>&1

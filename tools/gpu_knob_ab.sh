@@ -29,7 +29,7 @@ print("%-64s" % "TOTAL" + "".join("%10.4f" % r["total_ms"] for r in rows))
 for k in names[:16]:
     print("%-64s" % k[:64] + "".join("%10.4f" % r["kernels"].get(k, {"ms": float("nan")})["ms"] for r in rows))
 PY
-BENCH_PROFILE_OUT=$O/ops_r18.json step bench 400 python bench.py --model ${MODEL:-r18} --no-cpu-baseline --no-b1
+BENCH_PROFILE_OUT=$O/ops_r18.json step bench 400 python bench.py --full --model ${MODEL:-r18} --no-cpu-baseline --no-b1
 tail -1 $O/bench.log | cut -c1-600
-env $KNOB timeout -k 10 400 python bench.py --model ${MODEL:-r18} --no-cpu-baseline --no-b1 --allow-env-knobs --no-extras > $O/bench_knob.log 2>&1; echo "bench_knob rc=$?"
+env $KNOB timeout -k 10 400 python bench.py --full --model ${MODEL:-r18} --no-cpu-baseline --no-b1 --allow-env-knobs --no-extras > $O/bench_knob.log 2>&1; echo "bench_knob rc=$?"
 tail -1 $O/bench_knob.log | cut -c1-300
