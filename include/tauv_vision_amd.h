@@ -239,6 +239,48 @@ int tv_yolact_assemble_masks_indexed(const float* mask_prototype, const int64_t 
                                      int32_t A, const int64_t* det, const int32_t* counts, int32_t n_max, float* mask,
                                      void* stream);
 
+/* Depth localisation of detections: the per-detection loops of the two reference nodes that turn
+ * a detection into a camera-frame point, on the raw mono16 depth image. Device pointers, async on
+ * `stream`, no workspace, no host synchronisation (graph-capturable).
+ * depth [depth_batch, dh, dw] uint16 millimetres (depth_batch 1 broadcasts one image to all B). A
+ * pixel is selected when it lies in the detection's region and its depth is not 0; n_pixels is
+ * their number and sum_mm their exact 64-bit integer sum. depth_sum = sum_mm / 1000, z = sum_mm /
+ * n_pixels / 1000 (double). The detection is invalid if n_pixels == 0, depth_sum < min_depth_sum
+ * or z < min_z; otherwise x = (e_x - cx) * (z / fx), y = (e_y - cy) * (z / fy) (double).
+ * out [B, K, 8] fp32 (16-byte aligned): x, y, z, valid (1 / 0), n_pixels, depth_sum, e_x, e_y.
+ * Invalid rows carry x = y = z = 0 with their true n_pixels and depth_sum; rows k >= counts[b]
+ * are all zero. Every row is written by every call.
+ * TV_EINVAL: null pointers, non-positive sizes, depth_batch not 1 or B, fx or fy == 0.
+ * B * K == 0 succeeds and launches nothing.
+ *
+ * tv_localize_boxes (centernet_node.py:139-178: the cv2.rectangle mask of +-0.4 w, +-0.4 h around
+ * the centre, np.sum / np.mean of depth[(mask > 0) & (depth > 0)], the `< 10` and `z < 1`
+ * skips and the back-projection): records [B, K, rec_stride] as written by tv_decode (y, x, h, w
+ * in columns 2-5; rec_stride >= 6), counts [B]. In double, uncontracted, as the node's Python
+ * floats: e_x = x dw, e_y = y dh, corners trunc(e_x -+ box_scale w dw), trunc(e_y -+ box_scale h dh)
+ * (toward zero, like int()); the region is the filled rectangle between the corners, both
+ * inclusive, in either order, clipped to the image. The node hard-codes 640 x 360, its depth size;
+ * here dw, dh are the depth image's. A non-finite x, y, w or h selects nothing (valid = 0). The
+ * node passes fx, fy, cx, cy = M_projection[0,0], [1,1], [0,2], [1,2], min_depth_sum 10, min_z 1. */
+int tv_localize_boxes(const float* records, int32_t rec_stride, const int32_t* counts, int32_t B, int32_t K,
+                      const uint16_t* depth, int32_t depth_batch, int32_t dh, int32_t dw, double box_scale, double fx,
+                      double fy, double cx, double cy, double min_depth_sum, double min_z, float* out, void* stream);
+/* tv_localize_masks (yolact_node.py:135,143,177-193: F.interpolate (nearest) of every mask to the
+ * raw image size, the [n, H, W] copy to the host, np.nanmean(np.where(mask > 0.5, depth, nan)) with
+ * zero depth as NaN, and the back-projection): masks [B, n, mh, mw] fp32 contiguous, det [B, n]
+ * int64 and counts [B] as written by tv_yolact_fast_nms_batched, box [B, A, 4] (y, x, h, w);
+ * e_y = box[b, det, 0] dh, e_x = box[b, det, 1] dw. The region is every depth pixel (yy, xx) with
+ * masks[b, d, sy(yy), sx(xx)] > 0.5, sx(xx) = min((int)floorf((float)xx * ((float)mw / (float)dw)),
+ * mw - 1) and likewise sy — torch's nearest map, in fp32; the up-sampled mask is never stored. A
+ * det entry outside [0, A) gives an all-zero row. bound_by_box != 0 scans only the rows and columns
+ * that can map into the detection's box crop (for masks assembled with that box, which are zero
+ * outside it: the same result, fewer pixels read); 0 for masks assembled without a box. The node
+ * passes the camera intrinsics and min_depth_sum = min_z = 0. */
+int tv_localize_masks(const float* masks, int32_t mh, int32_t mw, const int32_t* counts, const int64_t* det,
+                      const float* box, int32_t A, int32_t B, int32_t n, const uint16_t* depth, int32_t depth_batch,
+                      int32_t dh, int32_t dw, int32_t bound_by_box, double fx, double fy, double cx, double cy,
+                      double min_depth_sum, double min_z, float* out, void* stream);
+
 /* Training targets of the CenterNet loss (loss.py:31-135), fp32, device pointers, async on `stream`.
  * generate_heatmap (loss.py:31-72): valid [B,n_objects] u8 (bool), label [B,n_objects] int64,
  *   center [B,n_objects,2] fp32 (y, x normalised) -> heatmap [B,n_labels,in_h/ratio,in_w/ratio]:

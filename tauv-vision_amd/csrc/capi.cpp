@@ -358,6 +358,22 @@ int tv_yolact_assemble_masks_indexed(const float* proto, const int64_t pst[4], i
   })
 }
 
+int tv_localize_boxes(const float* records, int32_t rec_stride, const int32_t* counts, int32_t B, int32_t K,
+                      const uint16_t* depth, int32_t depth_batch, int32_t dh, int32_t dw, double box_scale, double fx,
+                      double fy, double cx, double cy, double min_depth_sum, double min_z, float* out, void* stream) {
+  TV_GUARD({ return launch_localize_boxes(records, rec_stride, counts, B, K, depth, depth_batch, dh, dw, box_scale, fx,
+                                          fy, cx, cy, min_depth_sum, min_z, out, (hipStream_t)stream); })
+}
+
+int tv_localize_masks(const float* masks, int32_t mh, int32_t mw, const int32_t* counts, const int64_t* det,
+                      const float* box, int32_t A, int32_t B, int32_t n, const uint16_t* depth, int32_t depth_batch,
+                      int32_t dh, int32_t dw, int32_t bound_by_box, double fx, double fy, double cx, double cy,
+                      double min_depth_sum, double min_z, float* out, void* stream) {
+  TV_GUARD({ return launch_localize_masks(masks, mh, mw, counts, (const long long*)det, box, A, B, n, depth,
+                                          depth_batch, dh, dw, bound_by_box, fx, fy, cx, cy, min_depth_sum, min_z, out,
+                                          (hipStream_t)stream); })
+}
+
 int tv_decode_workspace_size(int32_t B, int32_t C, int32_t H, int32_t W, int32_t K, int64_t* bytes) {
   if (!bytes || B < 1 || C < 1 || H < 1 || W < 1 || K < 1) { set_error("bad argument"); return TV_EINVAL; }
   *bytes = (int64_t)decode_workspace_bytes(B, C, H, W, K);

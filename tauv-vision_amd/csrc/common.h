@@ -379,6 +379,17 @@ int launch_yolact_fast_nms(const float* cls, long long cls_bstride, int A, int C
 int launch_yolact_assemble_mask(const float* proto, const long long pst[4], int B, int K, int H, int W,
                                 const float* coeff, const float* box, const int* counts, const long long* det,
                                 int rows, int n_max, float* out, hipStream_t s);
+// Depth localisation of detections (localize.hip): records [B][K][rec_stride] (y, x, h, w in columns
+// 2-5) or masks [B][n][mh][mw] with det [B][n] rows of box [B][A][4], counts [B], depth
+// [depth_batch][dh][dw] u16 millimetres -> out [B][K or n][8]. Arguments are checked here (return 1
+// with the error text set); B * K == 0 launches nothing.
+int launch_localize_boxes(const float* records, int rec_stride, const int* counts, int B, int K, const uint16_t* depth,
+                          int depth_batch, int dh, int dw, double box_scale, double fx, double fy, double cx, double cy,
+                          double min_depth_sum, double min_z, float* out, hipStream_t s);
+int launch_localize_masks(const float* masks, int mh, int mw, const int* counts, const long long* det, const float* box,
+                          int A, int B, int n, const uint16_t* depth, int depth_batch, int dh, int dw, int bound_by_box,
+                          double fx, double fy, double cx, double cy, double min_depth_sum, double min_z, float* out,
+                          hipStream_t s);
 int launch_uncovered_copy(const void* add, int add_ldc, void* out, int out_ldc, int C, int B,
                           int tH, int tW, int y0, int y1, int x0, int x1, int dtype,
                           hipStream_t s);

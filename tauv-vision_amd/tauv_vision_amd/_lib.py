@@ -74,6 +74,10 @@ EXPORTS = {
                                   c_vp, c_vp], c_i32),
     "tv_yolact_assemble_masks_indexed": ([c_vp, ctypes.POINTER(c_i64), c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32,
                                           c_vp, c_vp, c_i32, c_vp, c_vp], c_i32),
+    "tv_localize_boxes": ([c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_f64, c_f64, c_f64, c_f64,
+                           c_f64, c_f64, c_f64, c_vp, c_vp], c_i32),
+    "tv_localize_masks": ([c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32,
+                           c_i32, c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_vp, c_vp], c_i32),
     "tv_train_heatmap": ([c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_vp, c_vp], c_i32),
     "tv_train_keypoint_targets": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                    c_f64, c_f64, c_vp, c_vp, c_vp, c_vp], c_i32),
