@@ -142,8 +142,12 @@ int tv_engine_insitu_read(tv_engine* engine, int32_t batch, void* stream, float*
 int tv_engine_forward_insitu(tv_engine* engine, const float* img_nchw, int32_t batch, float* out_nhwc, void* stream,
                              float* ms, int32_t cap, int32_t* n_slices);
 const char* tv_engine_op_label(tv_engine* engine, int32_t index);
-/* Kernel family launch `index` uses at this batch size ("conv_pipe", "conv_igemm", "conv_halo",
- * "prep"); "" before the batch's workspace exists. Diagnostic (roofline attribution). */
+/* What op `index` launches in a `batch`-frame workspace (its route): the kernel instance as a
+ * profiler demangles it, e.g. "tv::c3::conv3x3<_Float16, _Float16, 32, 1, 0, 0, 4, 4, 8>" (a
+ * split-K launch with " split-K n" appended; the stem kernels' input-mode argument follows the last
+ * profiled input kind), "prep" for the staging launch, or a parenthesised note for an op done
+ * inside another op's launch, e.g. "(fused into the 3x3 heads)". "" before the batch's workspace
+ * exists or past the last op. Diagnostic (roofline attribution, route table test). */
 const char* tv_engine_op_kernel(tv_engine* engine, int32_t batch, int32_t index);
 /* How a forward of `batch` frames is launched: as *n_slices (1..TV_MAX_SLICES) concurrent slices
  * of slice_batch[0..n_slices) frames, the rest of slice_batch zeroed (diagnostic: per-launch

@@ -4,6 +4,7 @@
 #include <string>
 #include <unordered_map>
 #include <utility>
+#include <variant>
 #include <vector>
 
 #include "common.h"
@@ -31,6 +32,34 @@ struct Packed {
   int head_row0[16] = {}, head_nrows[16] = {};
 };
 
+constexpr int kTile = 128;
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// The one thing that happens when an op's turn comes. Chosen by plan_schedule (schedule.cpp);
+// run_op, op_kernel, run_all's grouped launches and profile() switch on it.
+enum class Route : int {
+  Staging, StagingInStem,      // OP_PREP on its own | done by the stem kernel (stem.hip / stem_s2.hip)
+  Stem, StemS2, StemInS2,      // stem.hip | stem + block0.conv1 in one launch, on conv1's op | the stem op of that pair
+  LayoutIn, MaxPool, DcnSample, DwConvTAdd,
+  DcnFused, DcnInFused,        // DCNv2 sampling + column GEMM in one kernel, on the GEMM's op | its OP_DCN
+  HeadsFused, HeadsDone,       // stacked 3x3 heads with the 1x1 heads in the epilogue | those 1x1 heads' op
+  ConvT, ConvT3, ConvT3Done,   // convt.hip | all four phases from the phase-(0,0) op (convt3.hip) | the other three
+  ConvSmall, ConvBurst, ConvLat, Conv1x1, Conv3x3S2, Conv3x3, ConvPipe, ConvIgemm
+};
+struct C3Geom { int tw, grid, res, ni, nw; };  // conv3x3: tile width, workgroups, RES, channel fragments, waves
+struct S2Geom { int grid; };                   // conv3x3s2: persistent workgroups
+struct OpRoute {
+  Route kind = Route::ConvIgemm;
+  // the launch geometry of the route: Conv3x3 / HeadsFused, Conv3x3S2, ConvBurst, ConvT, ConvT3, DcnFused
+  std::variant<std::monostate, C3Geom, S2Geom, BurstParams, ConvTParams, ConvT3Params, DcnParams> geom;
+  int slot = 0;  // ConvLat: its place in a grouped launch (the split-K slab / ticket region)
+};
+
+// Between plan_schedule() and materialize() a pointer into the arena holds kArenaTag + its offset
+// (never null, so "no tensor" stays distinct; a non-canonical address, so one that materialize()
+// failed to bind cannot pass for memory); every other device pointer is still null.
+constexpr uintptr_t kArenaTag = uintptr_t(0xA5A5) << 48;
+
 struct Workspace {
   int B = 0;
   void* arena = nullptr;
@@ -38,39 +67,27 @@ struct Workspace {
   std::vector<size_t> off;          // per tensor
   std::vector<ConvParams> params;   // per op (host copy)
   ConvParams* dparams = nullptr;    // per op (device copy)
-  std::vector<int> use_pipe;        // per op: 1 = conv_pipe (256-pixel tiles), 0 = conv_igemm
-  std::vector<int> c3_tw, c3_grid;  // per op: > 0 = persistent conv3x3 (tile width, workgroups); overrides all
-  std::vector<int> c3_res;          // per op: 1 = conv3x3 with the 1x1 residual segment (RES)
-  std::vector<int> c3_ni;           // per op: channel fragments per wave (4: 128-channel tiles, 2: 64)
-  std::vector<int> c3_nw;           // per op: waves per workgroup (8: one per CU, 4: two per CU)
-  std::vector<int> s2_grid;         // per op: > 0 = persistent stride-2 conv3x3s2 (workgroups)
-  std::vector<int> head_fused;      // per op: 1 = stacked 3x3 heads with the 1x1 heads fused in
-  std::vector<int> head_skip;       // per op: 1 = block-diagonal 1x1 heads done by the op before
-  std::vector<int> small;           // per op: 1 = narrow-channel 3x3 conv on conv_small.hip
-  std::vector<int> lat;             // per op: 1 = split-K small-level GEMM on conv_lat.hip
-  std::vector<int> burst;           // per op: 1 = one-shot small-level conv on conv_burst.hip
-  std::vector<BurstParams> bparams; // per op: its conv_burst launch geometry
-  std::vector<int> c1x1;            // per op: 1 = streaming 1x1 conv (Roots) on conv1x1.hip
-  std::vector<int> dcn_skip;        // per op: 1 = DCN sampling done inside the next op's fused kernel
-  std::vector<DcnParams> dcn;       // per op: fused DCNv2 launch (dcn.hip) when dcn[i].x != null
-  std::vector<int> convt;           // per op: 1 = OP_CONVT_ADD on convt.hip
-  std::vector<ConvTParams> tparams; // per op: convt.hip launch parameters
-  std::vector<int> ct3;             // per op: 1 = ConvTranspose2d(3, s2) phase (0,0) launching all four on convt3.hip,
-                                    // 2 = a phase that launch covers
-  std::vector<ConvT3Params> ct3p;   // per op: convt3.hip launch parameters (ct3 == 1)
-  KStep* dks = nullptr;             // k-step descriptors of all pipelined ops
-  float* slab = nullptr;            // conv_lat split-K partial tiles (one region per slot of a grouped launch)
-  unsigned* cnt = nullptr;          // conv_lat split-K tickets, one per tile and slot, zeroed per forward
-  float* pslab = nullptr;           // conv_pipe split-K partial tiles (one layer at a time)
-  unsigned* pcnt = nullptr;         // conv_pipe split-K tickets, one per tile (reset by the last slice)
-  float* dslab = nullptr;           // dcn_gemm64 split-K partial accumulators (one layer at a time)
-  unsigned* dcnt = nullptr;         // dcn_gemm64 split-K tickets, one per tile (reset by the last slice)
+  std::vector<OpRoute> route;       // per op
+  std::vector<KStep> ksteps;        // k-step descriptors of the ConvPipe / ConvLat ops
+  std::vector<size_t> ks_off;       // per op: its first descriptor in `ksteps`
+  KStep* dks = nullptr;             // device copy of `ksteps`
+  // split-K hand-off: fp32 partial tiles (slab) and one ticket per tile (cnt), of conv_lat (per slot of a
+  // grouped launch, lat_slots of them), conv_pipe (p*) and dcn_gemm64 (d*; these two one layer at a time)
+  size_t lat_slab_floats = 0, lat_tickets = 0, pipe_slab_floats = 0, pipe_tickets = 0, dcn_slab_floats = 0, dcn_tickets = 0;
+  int lat_slots = 1;
+  float *slab = nullptr, *pslab = nullptr, *dslab = nullptr;
+  unsigned *cnt = nullptr, *pcnt = nullptr, *dcnt = nullptr;
   std::vector<int> level;           // per op: dependency level (the arena's time; plan order when not grouping)
   std::vector<int> order;           // the ops in execution order: by level, then plan order
   std::vector<std::vector<int>> groups;  // the schedule: conv_lat layers of one level in one launch, others alone
   size_t cnt_bytes = 0;
   std::vector<std::string> kname;   // per op: kernel instance name (diagnostics), filled lazily
   std::vector<hipEvent_t> gev;      // forward_insitu(): one event before each schedule group + one after the last
+
+  Workspace() = default;
+  Workspace(const Workspace&) = delete;  // owns its device memory and events ...
+  Workspace& operator=(const Workspace&) = delete;
+  ~Workspace();  // ... and frees them (no launch may still use them)
 };
 
 struct Engine {
@@ -177,7 +194,9 @@ struct Engine {
   int fold(const std::string& conv, const std::string& bn, int cout, std::vector<double>& scale,
            std::vector<double>& shift);
   int pack_op(size_t i);
-  int make_workspace(int B, Workspace* ws);
+  void plan_schedule(int B, Workspace* ws) const;  // schedule.cpp: every decision, no HIP call
+  int materialize(Workspace* ws);                  // the allocations, repacks, pointers and uploads of a planned workspace
+  int bind_op(size_t i, Workspace* ws);
   int run_op(size_t i, Workspace* ws, const void* input, int input_u8, float* out, hipStream_t s);
   int run_all(const void* input, int input_u8, int B, float* out, hipStream_t s, size_t op0 = 0,
               size_t op1 = (size_t)-1);

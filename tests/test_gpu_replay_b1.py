@@ -1,6 +1,6 @@
 """BASELINE config 2 (the latency path) as bench.py times it: the B=1 step — forward_u8 + device
 decode + async D2H of the records — captured once as a hipGraph and replayed (bench.py
-latency_b1). At B=1 the engine runs its latency-path schedule (engine.cpp make_workspace: ops by
+latency_b1). At B=1 the engine runs its latency-path schedule (schedule.cpp plan_schedule: ops by
 dependency level, grouped conv_lat / convt_add launches, conv_lat split-K slabs whose tickets are
 self-resetting: zeroed once when the workspace is made, and each tile's last-arriving slice zeroes
 its own ticket, so every complete replay leaves them at zero for the next — no memset node, which

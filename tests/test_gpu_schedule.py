@@ -1,4 +1,4 @@
-"""The engine's latency-path schedule (engine.cpp make_workspace): on workspaces of <= 8 frames
+"""The engine's latency-path schedule (schedule.cpp plan_levels, plan_groups): on workspaces of <= 8 frames
 the ops run by dependency level — the MultiIDAUp wavefront, the IDAUpReverse projections early
 (dla.py:265-284, 340-357, 377-390) — and the conv_lat layers / ConvTranspose up-steps of one level
 share a launch (conv_lat.hip conv_lat_group, convt.hip convt_add_group), the arena's lifetimes
