@@ -56,11 +56,41 @@ typedef enum tv_dtype { TV_F32 = 0, TV_F16 = 1, TV_BF16 = 2, TV_F32X3 = 3 } tv_d
  * DLABackbone alone (dla.py:393-416, DLABackbone.forward): the parameters are the "backbone.*"
  * keys of TV_ARCH_CENTERNET, n_heads / head_channels are ignored, and the output is the
  * IDAUpReverse feature map as fp32 NHWC [B, in_h / 2^downsamples, in_w / 2^downsamples,
- * channels[0]]. */
+ * channels[0]].
+ *
+ * TV_ARCH_YOLACT_HEAD = everything of Yolact.forward after the backbone (model.py:34-60):
+ * FeaturePyramid (feature_pyramid.py:8-58), Masknet on fpn[0] and the one PredictionHead
+ * (prediction_head.py:9-143) shared by every level; TV_ARCH_YOLACT_FPN = the FeaturePyramid alone.
+ * Both take several inputs and write several outputs (tv_engine_forward_multi; the single-pointer
+ * entry points return TV_EINVAL for them). Encoding:
+ *   n_levels            len(in_depths), the number of backbone maps (1..TV_MAX_IO)
+ *   channels[0]         feature_depth F;  channels[1 + i] = in_depths[i]
+ *   downsamples         n_fpn_downsample_layers (n_levels + downsamples <= TV_MAX_IO)
+ *   n_maps, map_h[i], map_w[i]   the size of backbone map i — independent inputs (a ResNet gives
+ *                       69 / 35 / 18 at 550 x 550, not exact halvings); n_maps must equal n_levels
+ *   in_h, in_w          ignored
+ *   TV_ARCH_YOLACT_HEAD only (ignored by TV_ARCH_YOLACT_FPN):
+ *   heights[0..3]       n_prediction_head_layers, n_classification_layers, n_box_layers, n_mask_layers
+ *   n_heads = 2, head_channels[0] = n_prototype_masks k, head_channels[1] = n_classes C
+ *   n_aspect_ratios     len(anchor_aspect_ratios) (>= 1)
+ * Inputs: backbone map i as fp32 NCHW [B, in_depths[i], map_h[i], map_w[i]].
+ * Outputs of TV_ARCH_YOLACT_FPN: level l < n_levels + downsamples as fp32 NHWC [B, h_l, w_l, F]
+ * (h_l = map_h[l] for the first n_levels, then (h + 1) / 2 per stride-2 level).
+ * Outputs of TV_ARCH_YOLACT_HEAD, all fp32 and contiguous, A = sum over levels of h_l w_l n_aspect_ratios:
+ *   0 classification [B, A, C + 1]   1 box_encoding [B, A, 4]   2 mask_coeff [B, A, k] (tanh applied)
+ *   3 mask_prototype NHWC [B, 4 map_h[0], 4 map_w[0], k rounded up to 4]
+ * Row order of 0-2: levels in order, within a level (y * w_l + x) * n_aspect_ratios + a — the
+ * reference's permute(0, 2, 3, 1).reshape (prediction_head.py:112-113). Parameters: the reference
+ * Yolact state_dict keys without "_backbone.*" ("_feature_pyramid.*", "_masknet.*",
+ * "_prediction_head.*"; the Bottleneck blocks in torchvision's layout conv1, bn1, conv2, bn2, conv3,
+ * bn3 with bias-free convs); for TV_ARCH_YOLACT_FPN the FeaturePyramid's own keys, unprefixed. */
 #define TV_ARCH_CENTERNET 0
 #define TV_ARCH_DLA34 1
 #define TV_ARCH_PROTONET 2
 #define TV_ARCH_CENTERNET_BACKBONE 3
+#define TV_ARCH_YOLACT_HEAD 4
+#define TV_ARCH_YOLACT_FPN 5
+#define TV_MAX_IO 8
 typedef struct tv_model_desc {
   int32_t n_levels;          /* len(backbone_heights) */
   int32_t heights[8];        /* backbone_heights */
@@ -71,6 +101,10 @@ typedef struct tv_model_desc {
   int32_t in_h, in_w;        /* ModelConfig.in_h / in_w */
   int32_t compute_dtype;     /* tv_dtype: TV_F32 = exact-f32 parity mode, TV_F32X3 its three-fp16-MFMA form */
   int32_t arch;              /* TV_ARCH_* */
+  /* TV_ARCH_YOLACT_HEAD / TV_ARCH_YOLACT_FPN only (zero for the other archs) */
+  int32_t n_maps;            /* number of (map_h, map_w) entries: must equal n_levels */
+  int32_t map_h[TV_MAX_IO], map_w[TV_MAX_IO];
+  int32_t n_aspect_ratios;   /* len(ModelConfig.anchor_aspect_ratios) */
 } tv_model_desc;
 
 typedef struct tv_engine tv_engine;
@@ -115,6 +149,21 @@ int tv_engine_prepare(tv_engine* engine, int32_t batch, void* stream);
 int tv_engine_trim(tv_engine* engine);
 /* Centernet.forward(img) -> Prediction heads (centernet.py:65-92). Async on `stream`. */
 int tv_engine_forward(tv_engine* engine, const float* img_nchw, int32_t batch, float* out_nhwc, void* stream);
+/* The caller's buffers of a desc, per frame: *n_in inputs, input i fp32 NCHW of in_shape[i] =
+ * (C, H, W); *n_out outputs, output j fp32 NHWC of out_shape[j] = (H, W, C, cpad) — cpad the stored
+ * channel count, C of them meaningful (a TV_ARCH_YOLACT_HEAD anchor-indexed output is (A, 1, width,
+ * width)). One of each for the single-input archs. */
+int tv_model_io(const tv_model_desc* desc, int32_t* n_in, int32_t in_shape[TV_MAX_IO][3], int32_t* n_out,
+                int32_t out_shape[TV_MAX_IO][4]);
+/* The forward of an arch with several inputs and outputs (any arch: n_in / n_out must be those of
+ * tv_model_io): inputs[i] / outputs[j] device pointers to `batch` frames each, contiguous. Async on
+ * `stream`; a batch that runs as concurrent slices advances every pointer by its own per-frame size. */
+int tv_engine_forward_multi(tv_engine* engine, const float* const* inputs, int32_t n_in, float* const* outputs,
+                            int32_t n_out, int32_t batch, void* stream);
+/* tv_engine_profile over the same buffers. */
+int tv_engine_profile_multi(tv_engine* engine, const float* const* inputs, int32_t n_in, float* const* outputs,
+                            int32_t n_out, int32_t batch, void* stream, float* ms, double* flops, int32_t cap,
+                            int32_t* n_ops);
 /* Same from raw u8 RGB frames with ToTensor + Normalize fused (centernet_node.py:90-92). */
 int tv_engine_forward_u8(tv_engine* engine, const uint8_t* frames_nhwc, int32_t batch, float* out_nhwc,
                          void* stream);
@@ -371,6 +420,15 @@ int tv_diag_conv_small(const void* src, int32_t B, int32_t H, int32_t W, int32_t
 int tv_diag_convt3(const void* src, int32_t B, int32_t H, int32_t W, int32_t C, int32_t ldc, const float* weight,
                    const float* bias, int32_t N, int32_t act, int32_t dtype, int32_t tile_w, int32_t tile_h, void* out,
                    int32_t out_ldc, void* stream);
+
+/* Diagnostics (GPU tests): the FeaturePyramid's top-down step (feature_pyramid.py:49-50) through
+ * bilinear_add, the engine's kernel for it: dst += F.interpolate(src, (dst_h, dst_w), mode="bilinear")
+ * (align_corners=False: source coordinate max(0, (d + 0.5) in / out - 0.5), second tap clamped to
+ * in - 1; any per-axis ratio), in place. src: compute-dtype NHWC [B, src_h, src_w, src_ldc], dst:
+ * compute-dtype NHWC [B, dst_h, dst_w, dst_ldc], C channels of each (C and both pixel strides whole
+ * 16-byte vectors, else TV_EINVAL). Async on `stream`; allocates nothing. */
+int tv_diag_bilinear_add(const void* src, int32_t B, int32_t src_h, int32_t src_w, int32_t src_ldc, void* dst,
+                         int32_t dst_h, int32_t dst_w, int32_t dst_ldc, int32_t C, int32_t dtype, void* stream);
 
 const char* tv_last_error(void);
 const char* tv_version(void);

@@ -77,6 +77,54 @@ int tv_model_geometry(const tv_model_desc* d, double* flops, int32_t* oh, int32_
   })
 }
 
+int tv_model_io(const tv_model_desc* d, int32_t* n_in, int32_t in_shape[TV_MAX_IO][3], int32_t* n_out,
+                int32_t out_shape[TV_MAX_IO][4]) {
+  TV_GUARD({
+    if (!d || !n_in || !in_shape || !n_out || !out_shape) { set_error("null argument"); return TV_EINVAL; }
+    Plan p;
+    int rc = build_plan(*d, &p);
+    if (rc) return rc;
+    *n_in = (int32_t)p.ins.size();
+    *n_out = (int32_t)p.outs.size();
+    for (size_t i = 0; i < p.ins.size() && i < TV_MAX_IO; ++i)
+      in_shape[i][0] = p.ins[i].C, in_shape[i][1] = p.ins[i].H, in_shape[i][2] = p.ins[i].W;
+    for (size_t i = 0; i < p.outs.size() && i < TV_MAX_IO; ++i)
+      out_shape[i][0] = p.outs[i].H, out_shape[i][1] = p.outs[i].W, out_shape[i][2] = p.outs[i].C,
+      out_shape[i][3] = p.outs[i].cpad;
+    return TV_OK;
+  })
+}
+
+int tv_engine_forward_multi(tv_engine* e, const float* const* inputs, int32_t n_in, float* const* outputs,
+                            int32_t n_out, int32_t B, void* stream) {
+  TV_GUARD({
+    if (!e) { set_error("null engine"); return TV_EINVAL; }
+    return e->e.forward_multi(reinterpret_cast<const void* const*>(inputs), n_in, outputs, n_out, 0, B,
+                              (hipStream_t)stream);
+  })
+}
+
+int tv_engine_profile_multi(tv_engine* e, const float* const* inputs, int32_t n_in, float* const* outputs,
+                            int32_t n_out, int32_t B, void* stream, float* ms, double* flops, int32_t cap,
+                            int32_t* n_ops) {
+  TV_GUARD({
+    if (!e || !ms || !flops || !n_ops) { set_error("null argument"); return TV_EINVAL; }
+    int n = 0;
+    int rc = e->e.profile_multi(reinterpret_cast<const void* const*>(inputs), n_in, outputs, n_out, 0, B,
+                                (hipStream_t)stream, ms, flops, cap, &n);
+    *n_ops = n;
+    return rc;
+  })
+}
+
+int tv_diag_bilinear_add(const void* src, int32_t B, int32_t src_h, int32_t src_w, int32_t src_ldc, void* dst,
+                         int32_t dst_h, int32_t dst_w, int32_t dst_ldc, int32_t C, int32_t dtype, void* stream) {
+  TV_GUARD({
+    return launch_bilinear_add(src, B, src_h, src_w, src_ldc, dst, dst_h, dst_w, dst_ldc, C, dtype,
+                               (hipStream_t)stream);
+  })
+}
+
 int tv_engine_create(const tv_model_desc* d, const tv_weight_view* w, int32_t n, int32_t device, tv_engine** out) {
   TV_GUARD({
     if (!d || !out || (n && !w)) { set_error("null argument"); return TV_EINVAL; }

@@ -379,6 +379,26 @@ int launch_yolact_fast_nms(const float* cls, long long cls_bstride, int A, int C
 int launch_yolact_assemble_mask(const float* proto, const long long pst[4], int B, int K, int H, int W,
                                 const float* coeff, const float* box, const int* counts, const long long* det,
                                 int rows, int n_max, float* out, hipStream_t s);
+// YOLACT neck and head (yolact_head.hip).
+// dst += bilinear(src -> dst's size), F.interpolate(mode="bilinear", align_corners=False), in place:
+// NHWC compute dtype, C channels and both pixel strides in whole 16-byte vectors
+int launch_bilinear_add(const void* src, int B, int hs, int ws, int src_ldc, void* dst, int hd, int wd, int dst_ldc,
+                        int C, int dtype, hipStream_t s);
+// One level's raw fp32 head tensors into the caller's anchor-indexed outputs: part j copies columns
+// [c0, c0 + n) of pixel (b, p) of src ([B, HW, ldc]) to dst[b * dst_frame + p * n + (0..n)), dst
+// already offset to the level's first row; tanh on request
+struct HeadScatterPart {
+  const float* src;
+  float* dst;
+  long long dst_frame;  // floats per frame of the output (A_total * width)
+  int ldc, c0, n, tanh;
+};
+constexpr int kScatterMaxParts = 3;
+struct HeadScatterParams {
+  HeadScatterPart part[kScatterMaxParts];
+  int nparts, B, HW;
+};
+int launch_head_scatter(const HeadScatterParams& p, hipStream_t s);
 // Depth localisation of detections (localize.hip): records [B][K][rec_stride] (y, x, h, w in columns
 // 2-5) or masks [B][n][mh][mw] with det [B][n] rows of box [B][A][4], counts [B], depth
 // [depth_batch][dh][dw] u16 millimetres -> out [B][K or n][8]. Arguments are checked here (return 1

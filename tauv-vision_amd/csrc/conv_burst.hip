@@ -98,8 +98,12 @@ __device__ __forceinline__ void burst_tile(const BurstParams& p, const int bid) 
   const f32x4 b0 = __builtin_bit_cast(f32x4, raw_buffer_load_v4(brs, boff, 0, 0));
   const f32x4 b1 = __builtin_bit_cast(f32x4, raw_buffer_load_v4(brs, boff + 16, 0, 0));
   const int nk = p.nk16;
-  const int kq0 = wave * ((nk + NW - 1) / NW);
-  const int nkw = max(0, min(KPW, nk - kq0));       // this wave's k-steps (wave-uniform)
+  // this wave's K quarter [kq0, kq0 + nkw) (wave-uniform). The quarter may be shorter than the
+  // compiled instance's KPW (nk = 8, a lone 128-channel 1x1: quarters of 2 on the KPW = 4 instance):
+  // bounded by the quarter, not by KPW, or neighbouring waves would sum the same k-steps twice
+  const int kq = (nk + NW - 1) / NW;
+  const int kq0 = wave * kq;
+  const int nkw = max(0, min(min(KPW, kq), nk - kq0));
   u32x4 wreg[KPW];
   {
     const i32x4 wr = rsrc_of(p.w, (unsigned)(p.ntiles * nk * 64 * 16));

@@ -82,7 +82,9 @@ int Engine::pack_op(size_t oi) {
   Packed& pk = packed[oi];
   const int esz = dtype_size(dtype);
   const int BK = 128 / esz;
-  if (op.kind == OP_PREP || op.kind == OP_MAXPOOL || op.kind == OP_DCN || op.kind == OP_LAYOUT_IN) return TV_OK;
+  if (op.kind == OP_PREP || op.kind == OP_MAXPOOL || op.kind == OP_DCN || op.kind == OP_LAYOUT_IN ||
+      op.kind == OP_BILINEAR_ADD || op.kind == OP_HEAD_SCATTER)
+    return TV_OK;
   if (op.kind == OP_DWCONVT_ADD) {  // depthwise ConvTranspose2d weight [C][1][2f][2f] -> fp32 [2f][2f][C]
     const int c = op.N, k = 2 * op.up_s;
     const float* w = weight(op.up_w + ".weight", (int64_t)c * k * k);
@@ -121,7 +123,7 @@ int Engine::pack_op(size_t oi) {
     const int N = op.N;
     // rows of the PyTorch weight: a plain conv into the caller's fp32 output stores out_cpad
     // columns of an out_c-channel conv (protonet _output_layer)
-    const int wN = (op.out < 0 && op.stack_w.empty()) ? plan.out_c : N;
+    const int wN = (op.out < 0 && op.stack_w.empty()) ? plan.outspec(op.out).C : N;
     pk.Npad = (int)align_up(N, kTile);
     int kbase = 0;
     pk.seg_ksteps.clear();
@@ -165,7 +167,17 @@ int Engine::pack_op(size_t oi) {
         const SegSpec& sg = op.segs[si];
         const int cs = plan.tensors[sg.src].C;
         if (sg.identity) {  // residual added as-is: identity 1x1 (exact in every compute dtype)
-          for (int co = 0; co < std::min(N, sg.cin); ++co) hw[(size_t)co * pk.Kpad + (size_t)kb * BK + co] = 1.f;
+          // ... or through an eval BatchNorm that follows a ReLU and so folds into no conv (YOLACT
+          // head blocks): the identity scaled per channel, the shift in the bias
+          std::vector<double> scale(N, 1.0), shift(N, 0.0);
+          if (!sg.bn.empty()) {
+            int rc = fold("", sg.bn, N, scale, shift);
+            if (rc) return rc;
+          }
+          for (int co = 0; co < std::min(N, sg.cin); ++co) {
+            hw[(size_t)co * pk.Kpad + (size_t)kb * BK + co] = (float)scale[co];
+            bias[co] += (float)shift[co];
+          }
           kb += pk.seg_ksteps[si];
           continue;
         }
@@ -610,14 +622,20 @@ int Engine::trim() {
   return TV_OK;
 }
 
-int Engine::run_op(size_t i, Workspace* ws, const void* input, int input_u8, float* out, hipStream_t s) {
+int Engine::run_op(size_t i, Workspace* ws, const IoPtrs& io, int input_u8, hipStream_t s) {
   const OpSpec& op = plan.ops[i];
   const OpRoute& r = ws->route[i];
   char* base = (char*)ws->arena;
   const ConvParams* dp = ws->dparams + i;
-  const bool out_f32 = op.out < 0, x3 = dtype == F32 && f32x3;
+  const bool out_f32 = op.out < 0 || op.out_f32, x3 = dtype == F32 && f32x3;
   const int mode = op.kind == OP_CONVT_ADD || op.up_s ? 1 : 0;
-  const size_t out_floats = (size_t)ws->B * plan.out_h * plan.out_w * plan.out_cpad;
+  // the caller's buffers this op touches: input op.io (staging / layout ops), output -1 - op.out
+  // (the fused heads launch writes the output of the 1x1 heads' op, the next one)
+  const void* input = io.in[op.io];
+  const int oslot = r.kind == Route::HeadsFused ? plan.ops[i + 1].out : op.out;
+  float* out = oslot < 0 ? io.out[-1 - oslot] : nullptr;
+  const IoSpec ospec = oslot < 0 ? plan.outspec(oslot) : IoSpec{};
+  const size_t out_floats = (size_t)ws->B * ospec.H * ospec.W * ospec.cpad;
   int rc = TV_OK;
   switch (r.kind) {
     case Route::StagingInStem:  // staging runs inside the stem kernel
@@ -655,8 +673,28 @@ int Engine::run_op(size_t i, Workspace* ws, const void* input, int input_u8, flo
         set_error("this model takes an fp32 NCHW feature map, not u8 frames");
         return TV_EINVAL;
       }
-      return launch_nchw_to_nhwc((const float*)input, ws->B, op.N, desc.in_h, desc.in_w, base + ws->off[op.out],
-                                 plan.tensors[op.out].C, dtype, s);
+      return launch_nchw_to_nhwc((const float*)input, ws->B, op.N, plan.ins[op.io].H, plan.ins[op.io].W,
+                                 base + ws->off[op.out], plan.tensors[op.out].C, dtype, s);
+    case Route::BilinearAdd: {
+      const TensorSpec& src = plan.tensors[op.src];
+      const TensorSpec& dst = plan.tensors[op.out];
+      return launch_bilinear_add(base + ws->off[op.src], ws->B, src.H, src.W, src.C, base + ws->off[op.out], dst.H,
+                                 dst.W, dst.C, op.N, dtype, s);
+    }
+    case Route::HeadScatter: {
+      HeadScatterParams hp{};
+      hp.nparts = (int)op.parts.size();
+      hp.B = ws->B;
+      for (int k = 0; k < hp.nparts; ++k) {
+        const ScatterPart& q = op.parts[k];
+        const TensorSpec& t = plan.tensors[q.src];
+        const long long frame = (long long)plan.outs[q.slot].H * q.width;
+        hp.HW = t.H * t.W;
+        hp.part[k] = HeadScatterPart{(const float*)(base + ws->off[q.src]), io.out[q.slot] + (size_t)q.row0 * q.width,
+                                     frame, t.C, q.c0, q.n, q.tanh ? 1 : 0};
+      }
+      return launch_head_scatter(hp, s);
+    }
     case Route::MaxPool:
     case Route::DcnSample:
     case Route::DwConvTAdd: {
@@ -705,7 +743,7 @@ int Engine::run_op(size_t i, Workspace* ws, const void* input, int input_u8, flo
     case Route::ConvPipe:
     case Route::ConvIgemm: {
       ConvParams p = ws->params[i];
-      if (out_f32) p.out = out;  // the caller's fp32 output (only these two routes may write it directly)
+      if (op.out < 0) p.out = out;  // the caller's fp32 output (only these two routes may write it directly)
       rc = r.kind == Route::ConvPipe ? launch_conv_pipe(p, dp, p.out, dtype, out_f32, mode, s, x3)
                                      : launch_conv(p, dp, p.out, dtype, out_f32, mode, s);
       break;
@@ -749,7 +787,7 @@ std::vector<int> Engine::slice_sizes(int B) const {
   return {B};
 }
 
-int Engine::run_all(const void* input, int input_u8, int B, float* out, hipStream_t s, size_t op0, size_t op1) {
+int Engine::run_all(const IoPtrs& io, int input_u8, int B, hipStream_t s, size_t op0, size_t op1) {
   Workspace* ws = nullptr;
   int rc = get_workspace(B, s, &ws);
   if (rc) return rc;
@@ -770,7 +808,7 @@ int Engine::run_all(const void* input, int input_u8, int B, float* out, hipStrea
       ++gi;
       const Route kind = ws->route[g[0]].kind;
       if (g.size() == 1) {
-        rc = run_op((size_t)g[0], ws, input, input_u8, out, s);
+        rc = run_op((size_t)g[0], ws, io, input_u8, s);
       } else if (kind == Route::ConvBurst) {
         const BurstParams* bp[kBurstGroupMax];
         for (size_t k = 0; k < g.size(); ++k) bp[k] = &std::get<BurstParams>(ws->route[g[k]].geom);
@@ -794,7 +832,7 @@ int Engine::run_all(const void* input, int input_u8, int B, float* out, hipStrea
     return TV_OK;
   }
   for (size_t k = op0; k < nops && k < op1; ++k) {  // positions op0 .. op1 - 1 of the execution order
-    rc = run_op((size_t)ws->order[k], ws, input, input_u8, out, s);
+    rc = run_op((size_t)ws->order[k], ws, io, input_u8, s);
     if (rc) return rc;
   }
   return TV_OK;
@@ -816,15 +854,40 @@ int Engine::prepare(int B, hipStream_t s) {
   return get_workspace(sz[0], s, &ws);
 }
 
-int Engine::forward(const void* input, int input_u8, int B, float* out, hipStream_t s) {
+// The caller's pointer arrays -> IoPtrs, refusing a count that is not the plan's
+int Engine::check_io(const void* const* inputs, int n_in, float* const* outputs, int n_out, int B, IoPtrs* io) {
   if (B < 1) {
     set_error("batch must be >= 1");
     return TV_EINVAL;
   }
-  if (!input || !out) {
+  if (n_in != (int)plan.ins.size() || n_out != (int)plan.outs.size()) {
+    set_error("this model takes " + std::to_string(plan.ins.size()) + " input(s) and writes " +
+              std::to_string(plan.outs.size()) + " output(s), got " + std::to_string(n_in) + " and " +
+              std::to_string(n_out) + (n_in == 1 && n_out == 1 ? " (use tv_engine_forward_multi)" : ""));
+    return TV_EINVAL;
+  }
+  bool ok = inputs && outputs;
+  for (int i = 0; ok && i < n_in; ++i) ok = (io->in[i] = inputs[i]) != nullptr;
+  for (int i = 0; ok && i < n_out; ++i) ok = (io->out[i] = outputs[i]) != nullptr;
+  if (!ok) {
     set_error("null input/output pointer");
     return TV_EINVAL;
   }
+  return TV_OK;
+}
+
+int Engine::forward(const void* input, int input_u8, int B, float* out, hipStream_t s) {
+  return forward_multi(&input, 1, &out, 1, input_u8, B, s);
+}
+
+int Engine::forward_multi(const void* const* inputs, int n_in, float* const* outputs, int n_out, int input_u8, int B,
+                          hipStream_t s) {
+  IoPtrs io;
+  int rc = check_io(inputs, n_in, outputs, n_out, B, &io);
+  return rc ? rc : forward_io(io, input_u8, B, s);
+}
+
+int Engine::forward_io(const IoPtrs& io, int input_u8, int B, hipStream_t s) {
   TV_HIP(hipSetDevice(device));
   const std::vector<int> sz = slice_sizes(B);
   if (sz.size() > 1) {
@@ -833,26 +896,37 @@ int Engine::forward(const void* input, int input_u8, int B, float* out, hipStrea
     SideStreams* ss = nullptr;
     int rc = get_side(s, (int)sz.size() - 1, &ss);
     if (rc) return rc;
-    const size_t in_frame = input_u8 ? (size_t)desc.in_h * desc.in_w * 3
-                                     : (size_t)plan.in_channels * desc.in_h * desc.in_w * 4;
-    const size_t out_frame = (size_t)plan.out_h * plan.out_w * plan.out_cpad;
+    // the buffers of the slice that starts at frame f0: every pointer advanced by its own frame size
+    auto from = [&](size_t f0) {
+      IoPtrs q;
+      for (size_t i = 0; i < plan.ins.size(); ++i) {
+        const IoSpec& t = plan.ins[i];
+        const size_t in_frame = input_u8 ? (size_t)t.H * t.W * 3 : (size_t)t.C * t.H * t.W * 4;
+        q.in[i] = (const char*)io.in[i] + f0 * in_frame;
+      }
+      for (size_t i = 0; i < plan.outs.size(); ++i) {
+        const IoSpec& t = plan.outs[i];
+        q.out[i] = io.out[i] + f0 * ((size_t)t.H * t.W * t.cpad);
+      }
+      return q;
+    };
     // (diagnostic TV_SLICE_LAG = L: the other slices start once slice 0 has run its first L
     // ops, so that their heavy first layers meet slice 0's latency-bound deep levels — measured
     // slower: 4647 frames/s at L = 0, 4465 / 4338 / 4311 at L = 26 / 56 / 64, profiles/r4r)
     const size_t lag = std::min((size_t)slice_lag, plan.ops.size());
     if (lag) {
-      rc = run_all(input, input_u8, sz[0], out, s, 0, lag);
+      rc = run_all(io, input_u8, sz[0], s, 0, lag);
       if (rc) return rc;
     }
     TV_HIP(hipEventRecord(ss->fork, s));
     size_t f0 = (size_t)sz[0];
     for (size_t k = 1; k < sz.size(); ++k) {
       TV_HIP(hipStreamWaitEvent(ss->s[k - 1], ss->fork, 0));
-      rc = run_all((const char*)input + f0 * in_frame, input_u8, sz[k], out + f0 * out_frame, ss->s[k - 1]);
+      rc = run_all(from(f0), input_u8, sz[k], ss->s[k - 1]);
       if (rc) return rc;
       f0 += (size_t)sz[k];
     }
-    rc = run_all(input, input_u8, sz[0], out, s, lag, plan.ops.size());
+    rc = run_all(io, input_u8, sz[0], s, lag, plan.ops.size());
     if (rc) return rc;
     for (size_t k = 1; k < sz.size(); ++k) {
       TV_HIP(hipEventRecord(ss->join[k - 1], ss->s[k - 1]));
@@ -860,7 +934,7 @@ int Engine::forward(const void* input, int input_u8, int B, float* out, hipStrea
     }
     return TV_OK;
   }
-  return run_all(input, input_u8, B, out, s);
+  return run_all(io, input_u8, B, s);
 }
 
 int Engine::forward_insitu(const void* input, int input_u8, int B, float* out, hipStream_t s, float* ms, int cap,
@@ -917,7 +991,7 @@ const char* Engine::op_kernel(int B, size_t i) {
     static const char* tn[3] = {"float", "_Float16", "__bf16"};
     const OpSpec& op = plan.ops[i];
     const OpRoute& r = ws->route[i];
-    const std::string t = tn[dtype], o = op.out < 0 ? "float" : tn[dtype];
+    const std::string t = tn[dtype], o = op.out < 0 || op.out_f32 ? "float" : tn[dtype];
     const std::string mode = std::to_string(op.kind == OP_CONVT_ADD || op.up_s ? 1 : 0);
     const std::string smode = std::to_string(profiled_u8 ? (desc.in_w % 4 == 0 ? 2 : 1) : 0);  // input kind of the last profile()
     const char* x3 = dtype == F32 && f32x3 ? ", true>" : ">";
@@ -930,6 +1004,8 @@ const char* Engine::op_kernel(int B, size_t i) {
       case Route::StemS2: name = "tv::ss2::stem_s2<" + t + ", " + smode + ">"; break;
       case Route::Stem: name = "tv::stem::stem_conv<" + t + ", " + smode + ", " + (op.N <= 32 ? "1" : "4") + ">"; break;
       case Route::LayoutIn: name = "tv::nchw_to_nhwc<" + t + ">"; break;
+      case Route::BilinearAdd: name = "tv::yh::bilinear_add<" + t + ">"; break;
+      case Route::HeadScatter: name = "tv::yh::head_scatter"; break;
       case Route::MaxPool: name = "tv::dla::maxpool2_ceil<" + t + ">"; break;
       case Route::DcnSample: name = "tv::dla::dcn_sample<" + t + ">"; break;
       case Route::DwConvTAdd: name = "tv::dla::dwconvt_add<" + t + ">"; break;
@@ -991,6 +1067,18 @@ const char* Engine::op_kernel(int B, size_t i) {
 
 int Engine::profile(const void* input, int input_u8, int B, float* out, hipStream_t s, float* ms, double* flops,
                     int cap, int* n_ops) {
+  return profile_multi(&input, 1, &out, 1, input_u8, B, s, ms, flops, cap, n_ops);
+}
+
+int Engine::profile_multi(const void* const* inputs, int n_in, float* const* outputs, int n_out, int input_u8, int B,
+                          hipStream_t s, float* ms, double* flops, int cap, int* n_ops) {
+  IoPtrs io;
+  int rc = check_io(inputs, n_in, outputs, n_out, B, &io);
+  return rc ? rc : profile_io(io, input_u8, B, s, ms, flops, cap, n_ops);
+}
+
+int Engine::profile_io(const IoPtrs& io, int input_u8, int B, hipStream_t s, float* ms, double* flops, int cap,
+                       int* n_ops) {
   profiled_u8 = input_u8;
   TV_HIP(hipSetDevice(device));
   Workspace* ws = nullptr;
@@ -1002,7 +1090,7 @@ int Engine::profile(const void* input, int input_u8, int B, float* out, hipStrea
   // one op per launch, in execution order (each op's time between its neighbours' events)
   TV_HIP(hipEventRecord(ev[0], s));
   for (size_t k = 0; k < n; ++k) {
-    rc = run_op((size_t)ws->order[k], ws, input, input_u8, out, s);
+    rc = run_op((size_t)ws->order[k], ws, io, input_u8, s);
     if (rc) {  // name the op (with AMD_SERIALIZE_KERNEL=3 a faulting launch reports here)
       set_error("op " + std::to_string(ws->order[k]) + " (" + plan.ops[ws->order[k]].label + "): " + tv_last_error());
       break;

@@ -41,6 +41,7 @@ enum class Route : int {
   Staging, StagingInStem,      // OP_PREP on its own | done by the stem kernel (stem.hip / stem_s2.hip)
   Stem, StemS2, StemInS2,      // stem.hip | stem + block0.conv1 in one launch, on conv1's op | the stem op of that pair
   LayoutIn, MaxPool, DcnSample, DwConvTAdd,
+  BilinearAdd, HeadScatter,    // yolact_head.hip: the FPN's top-down step | raw head tensors -> the caller's outputs
   DcnFused, DcnInFused,        // DCNv2 sampling + column GEMM in one kernel, on the GEMM's op | its OP_DCN
   HeadsFused, HeadsDone,       // stacked 3x3 heads with the 1x1 heads in the epilogue | those 1x1 heads' op
   ConvT, ConvT3, ConvT3Done,   // convt.hip | all four phases from the phase-(0,0) op (convt3.hip) | the other three
@@ -59,6 +60,12 @@ struct OpRoute {
 // (never null, so "no tensor" stays distinct; a non-canonical address, so one that materialize()
 // failed to bind cannot pass for memory); every other device pointer is still null.
 constexpr uintptr_t kArenaTag = uintptr_t(0xA5A5) << 48;
+
+// The caller's buffers of one forward: plan.ins.size() inputs, plan.outs.size() outputs
+struct IoPtrs {
+  const void* in[kMaxIO] = {};
+  float* out[kMaxIO] = {};
+};
 
 struct Workspace {
   int B = 0;
@@ -177,8 +184,14 @@ struct Engine {
   int get_workspace(int B, hipStream_t s, Workspace** out);
   int prepare(int B, hipStream_t s);  // workspaces (and side stream) for forward(B) on s
   int trim();                         // free every cached workspace (no forward may be in flight)
+  // the single-pointer forms: archs with one input and one output only (TV_EINVAL otherwise)
   int forward(const void* input, int input_u8, int B, float* out, hipStream_t s);
   int profile(const void* input, int input_u8, int B, float* out, hipStream_t s, float* ms, double* flops, int cap, int* n_ops);
+  // every arch: n_in / n_out must be the plan's
+  int forward_multi(const void* const* inputs, int n_in, float* const* outputs, int n_out, int input_u8, int B,
+                    hipStream_t s);
+  int profile_multi(const void* const* inputs, int n_in, float* const* outputs, int n_out, int input_u8, int B,
+                    hipStream_t s, float* ms, double* flops, int cap, int* n_ops);
   // the forward as it runs (concurrent slices, schedule groups) with an event before each launch on
   // its slice's stream: ms[k * cap + i] = launch time of op i in slice k (a grouped launch's time on
   // its first op), *n_slices slices, synchronous (diagnostic: in-situ per-launch durations)
@@ -197,9 +210,11 @@ struct Engine {
   void plan_schedule(int B, Workspace* ws) const;  // schedule.cpp: every decision, no HIP call
   int materialize(Workspace* ws);                  // the allocations, repacks, pointers and uploads of a planned workspace
   int bind_op(size_t i, Workspace* ws);
-  int run_op(size_t i, Workspace* ws, const void* input, int input_u8, float* out, hipStream_t s);
-  int run_all(const void* input, int input_u8, int B, float* out, hipStream_t s, size_t op0 = 0,
-              size_t op1 = (size_t)-1);
+  int check_io(const void* const* inputs, int n_in, float* const* outputs, int n_out, int B, IoPtrs* io);
+  int forward_io(const IoPtrs& io, int input_u8, int B, hipStream_t s);
+  int profile_io(const IoPtrs& io, int input_u8, int B, hipStream_t s, float* ms, double* flops, int cap, int* n_ops);
+  int run_op(size_t i, Workspace* ws, const IoPtrs& io, int input_u8, hipStream_t s);
+  int run_all(const IoPtrs& io, int input_u8, int B, hipStream_t s, size_t op0 = 0, size_t op1 = (size_t)-1);
   int get_side(hipStream_t s, int n, SideStreams** out);
 };
 

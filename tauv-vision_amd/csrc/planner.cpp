@@ -321,12 +321,24 @@ struct Walker {
 
 }  // namespace
 
+static int build_plan_arch(const tv_model_desc& d, Plan* plan);
+
 int build_plan(const tv_model_desc& d0, Plan* plan) {
   // TV_F32X3 plans as TV_F32 (fp32 storage; only the engine's GEMM kernel choice differs)
   tv_model_desc d = d0;
   if (d.compute_dtype == TV_F32X3) d.compute_dtype = TV_F32;
+  int rc = build_plan_arch(d, plan);
+  if (rc) return rc;
+  // the single-input single-output archs: their one input frame and output tensor
+  if (plan->ins.empty()) plan->ins.push_back(IoSpec{d.in_h, d.in_w, plan->in_channels, plan->in_channels});
+  if (plan->outs.empty()) plan->outs.push_back(IoSpec{plan->out_h, plan->out_w, plan->out_c, plan->out_cpad});
+  return TV_OK;
+}
+
+static int build_plan_arch(const tv_model_desc& d, Plan* plan) {
   if (d.arch == TV_ARCH_DLA34) return build_plan_dla34(d, plan);
   if (d.arch == TV_ARCH_PROTONET) return build_plan_protonet(d, plan);
+  if (d.arch == TV_ARCH_YOLACT_HEAD || d.arch == TV_ARCH_YOLACT_FPN) return build_plan_yolact_head(d, plan);
   if (d.arch != TV_ARCH_CENTERNET && d.arch != TV_ARCH_CENTERNET_BACKBONE) {
     set_error("unknown model arch");
     return TV_EINVAL;

@@ -45,7 +45,20 @@ enum OpKind {
                      // sigmoid(mask logits) in tensor `add` (18 offsets, 9 logits; :386-392)
   OP_DWCONVT_ADD = 5, // depthwise ConvTranspose2d(2f, f, f//2) of `src` + pad_to_match + `add`
                       // (IDAUp, :446-451); up_s = f, (sy, sx) = (pad_above, pad_left)
-  OP_LAYOUT_IN = 6    // fp32 NCHW input with N channels -> NHWC compute dtype (protonet fpn[0] input)
+  OP_LAYOUT_IN = 6,   // fp32 NCHW input `io` with N channels -> NHWC compute dtype (protonet fpn[0] input,
+                      // the YOLACT neck's backbone maps)
+  // YOLACT neck and head (planner_yolact_head.cpp)
+  OP_BILINEAR_ADD = 7, // out += F.interpolate(src, size of out, "bilinear") in place (feature_pyramid.py:49-50)
+  OP_HEAD_SCATTER = 8  // one level's fp32 raw head tensors -> the caller's [A_total, width] outputs (`parts`)
+};
+
+// One part of an OP_HEAD_SCATTER: columns [c0, c0 + n) of the fp32 NHWC tensor `src` ([H, W, ldc],
+// n = n_ar * width) are, per frame, rows [row0, row0 + H W n_ar) of output `slot` ([A_total, width]
+// contiguous): pixel p's n values land at (row0 * width + p * n), which is the reference's
+// permute(0, 2, 3, 1).reshape order (prediction_head.py:112-113), aspect ratio innermost.
+struct ScatterPart {
+  int src, c0, n, slot, row0, width;
+  bool tanh;  // mask coefficients (prediction_head.py:141)
 };
 
 struct OpSpec {
@@ -72,11 +85,22 @@ struct OpSpec {
   // a second output tensor (the fused stem + block0.conv1 launch also writes the stem at the even
   // pixels, the block's residual input): placed and kept live like `out`
   int out2 = -1;
+  int io = 0;            // OP_LAYOUT_IN: which of the caller's inputs
+  bool out_f32 = false;  // OP_CONV into an fp32 arena tensor (TensorSpec::f32): the generic GEMMs' fp32 store
+  std::vector<ScatterPart> parts;  // OP_HEAD_SCATTER
 };
 
 struct TensorSpec {
   int H, W, C;  // per frame, stored channels (ldc == C)
+  bool f32 = false;  // fp32 elements in every compute dtype (the raw head logits)
 };
+
+// One of the caller's buffers, per frame: an input is fp32 NCHW [C, H, W]; an output fp32 NHWC
+// [H, W, cpad] of which C channels are meaningful.
+struct IoSpec {
+  int H, W, C, cpad;
+};
+constexpr int kMaxIO = 8;  // == TV_MAX_IO
 
 struct Plan {
   std::vector<ParamInfo> params;     // reference state_dict order
@@ -87,11 +111,19 @@ struct Plan {
   int in_channels = 3;               // channels of one input frame (fp32 NCHW path)
   double flops_per_frame = 0;
   std::set<std::string> names;       // every key of `params`
+  // the caller's buffers (build_plan fills one of each from in_channels / desc.in_h, in_w and
+  // out_* for the single-input single-output archs); an op's out < 0 is output -1 - out
+  std::vector<IoSpec> ins, outs;
+  const IoSpec& outspec(int out) const { return outs[-1 - out]; }
 };
 
 // Returns 0 or a TV_E* code (with tv_last_error set).
 int build_plan(const tv_model_desc& d, Plan* plan);
 int build_plan_dla34(const tv_model_desc& d, Plan* plan);  // planner_dla34.cpp
 int build_plan_protonet(const tv_model_desc& d, Plan* plan);  // planner_protonet.cpp
+// Masknet's parameters (keys prefixed) and its forward over the NHWC tensor `x` ([H, W, F]) appended
+// to a plan, the prototypes going to the caller's output `out_slot`; returns their IoSpec
+IoSpec append_protonet(Plan& P, const std::string& prefix, int x, int F, int k, int out_slot);
+int build_plan_yolact_head(const tv_model_desc& d, Plan* plan);  // planner_yolact_head.cpp
 
 }  // namespace tv

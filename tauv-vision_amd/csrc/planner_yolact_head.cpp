@@ -1,0 +1,298 @@
+// Planner for everything of the reference Yolact.forward after the backbone (model.py:34-60):
+// FeaturePyramid (feature_pyramid.py:8-58), the one PredictionHead shared by every level
+// (prediction_head.py:9-143) and Masknet on fpn[0] (planner_protonet.cpp), and for the
+// FeaturePyramid alone (TV_ARCH_YOLACT_FPN).
+//  (1) parameter registration order = Yolact.state_dict() without `_backbone.*` (model.py:25-29):
+//      `_feature_pyramid.` {`_lateral_layers.i`, `_downsample_layers.i`, `_prediction_layers.i`},
+//      `_masknet.*`, `_prediction_head.` {per group trunk / classification / box / mask:
+//      `_X_layers.i` (torchvision Bottleneck: conv1, bn1, conv2, bn2, conv3, bn3, bias-free convs),
+//      `_X_conv_layers.i`, `_X_bn_layers.i`; then `_classification_layer`, `_box_encoding_layer`,
+//      `_mask_coeff_layer`};
+//  (2) the forward pass lowered over NHWC tensors:
+//        * backbone map i fp32 NCHW -> NHWC compute dtype       -> OP_LAYOUT_IN (input i)
+//        * lateral 1x1 convs                                    -> one GEMM each
+//        * p_i = lateral_i + bilinear(p_{i+1})                  -> OP_BILINEAR_ADD, in place
+//        * 3x3 (+ stride-2 3x3 for the extra levels) + LeakyReLU -> one GEMM each
+//        * per level, x = relu(conv1x1(x) + BN(Bottleneck(x))) -> four GEMMs: the Bottleneck's three
+//          convs (BN folded, its residual an identity K-segment), then the 1x1 conv with the
+//          Bottleneck output as a second K-segment: the outer BatchNorm follows a ReLU, so it cannot
+//          fold into a conv — it is an identity segment scaled per channel, its shift in the bias
+//        * the three final 3x3 convs -> fp32 raw tensors in the arena (the GEMMs' fp32 store: the
+//          logits and box regressions are never rounded to the compute dtype); one GEMM with the
+//          weights stacked along N when no branch has blocks of its own
+//        * raw tensors -> the caller's [A_total, width] outputs -> OP_HEAD_SCATTER per level
+// Two reference quirks are kept: one PredictionHead for all levels (each level's ops read the same
+// weights), and the pixel-major, aspect-ratio-inner row order of permute(0, 2, 3, 1).reshape
+// (prediction_head.py:112-113), which differs from get_anchor's ratio-major blocks (anchors.py).
+#include "common.h"
+#include "planner.h"
+
+namespace tv {
+namespace {
+
+struct HeadWalker {
+  const tv_model_desc& d;
+  Plan& P;
+  const int F;
+  const bool head;
+
+  void add(const std::string& n, std::vector<int64_t> s) { P.params.push_back({n, std::move(s)}); }
+  void conv_p(const std::string& p, int cout, int cin, int k, bool bias = true) {
+    add(p + ".weight", {cout, cin, k, k});
+    if (bias) add(p + ".bias", {cout});
+  }
+  void bn_p(const std::string& p, int c) {
+    add(p + ".weight", {c});
+    add(p + ".bias", {c});
+    add(p + ".running_mean", {c});
+    add(p + ".running_var", {c});
+    add(p + ".num_batches_tracked", {});
+  }
+  void fpn_params(const std::string& p) {
+    for (int i = 0; i < d.n_levels; ++i) conv_p(p + "_lateral_layers." + std::to_string(i), F, d.channels[1 + i], 1);
+    for (int i = 0; i < d.downsamples; ++i) conv_p(p + "_downsample_layers." + std::to_string(i), F, F, 3);
+    for (int i = 0; i < d.n_levels; ++i) conv_p(p + "_prediction_layers." + std::to_string(i), F, F, 3);
+  }
+  void group_params(const std::string& p, const std::string& g, int n) {
+    for (int i = 0; i < n; ++i) {
+      const std::string b = p + g + "_layers." + std::to_string(i);
+      conv_p(b + ".conv1", F / 4, F, 1, false);
+      bn_p(b + ".bn1", F / 4);
+      conv_p(b + ".conv2", F / 4, F / 4, 3, false);
+      bn_p(b + ".bn2", F / 4);
+      conv_p(b + ".conv3", F, F / 4, 1, false);
+      bn_p(b + ".bn3", F);
+    }
+    for (int i = 0; i < n; ++i) conv_p(p + g + "_conv_layers." + std::to_string(i), F, F, 1);
+    for (int i = 0; i < n; ++i) bn_p(p + g + "_bn_layers." + std::to_string(i), F);
+  }
+
+  int tensor(int H, int W, int C, bool f32 = false) {
+    TensorSpec t{H, W, C};
+    t.f32 = f32;
+    P.tensors.push_back(t);
+    return (int)P.tensors.size() - 1;
+  }
+  int conv(const std::string& label, std::vector<SegSpec> segs, int N, int act) {
+    const TensorSpec s0 = P.tensors[segs[0].src];
+    const int Ho = (s0.H + 2 * segs[0].pad - segs[0].kh) / segs[0].stride + 1;
+    const int Wo = (s0.W + 2 * segs[0].pad - segs[0].kw) / segs[0].stride + 1;
+    OpSpec op;
+    op.kind = OP_CONV;
+    op.label = label;
+    op.N = N;
+    op.act = act;
+    for (const SegSpec& sg : segs) op.flops += 2.0 * Ho * Wo * N * (double)(sg.kh * sg.kw * sg.cin);
+    op.segs = std::move(segs);
+    op.out = tensor(Ho, Wo, N);
+    P.ops.push_back(op);
+    return op.out;
+  }
+  static SegSpec seg(int src, const std::string& w, const std::string& bn, int cin, int k, int stride) {
+    return SegSpec{src, w, bn, 0, cin, k, k, stride, k / 2};
+  }
+  // `src` added as it is (bn empty) or through an eval BatchNorm (scaled per channel, shift in the bias)
+  static SegSpec identity(int src, int c, const std::string& bn) {
+    SegSpec sg{src, "", bn, 0, c, 1, 1, 1, 0};
+    sg.identity = true;
+    return sg;
+  }
+
+  // feature_pyramid.py:44-58 -> the FPN levels' tensors
+  std::vector<int> fpn(const std::string& p) {
+    const int n = d.n_levels;
+    std::vector<int> lat(n);
+    for (int i = 0; i < n; ++i) {
+      const int c = d.channels[1 + i];
+      const int x = tensor(d.map_h[i], d.map_w[i], c);
+      P.ins.push_back(IoSpec{d.map_h[i], d.map_w[i], c, c});
+      OpSpec op;
+      op.kind = OP_LAYOUT_IN;
+      op.label = "backbone map " + std::to_string(i) + " NCHW fp32 -> NHWC";
+      op.out = x;
+      op.N = c;
+      op.io = i;
+      P.ops.push_back(op);
+      const std::string w = p + "_lateral_layers." + std::to_string(i);
+      lat[i] = conv(w, {seg(x, w, "", c, 1, 1)}, F, 0);
+    }
+    for (int i = n - 2; i >= 0; --i) {
+      OpSpec op;
+      op.kind = OP_BILINEAR_ADD;
+      op.label = "pyramid " + std::to_string(i) + " = lateral + bilinear(pyramid " + std::to_string(i + 1) + ")";
+      op.src = lat[i + 1];
+      op.add = lat[i];
+      op.out = lat[i];
+      op.N = F;
+      op.act = 0;
+      P.ops.push_back(op);
+    }
+    std::vector<int> lv;
+    for (int i = 0; i < n; ++i) {
+      const std::string w = p + "_prediction_layers." + std::to_string(i);
+      lv.push_back(conv(w + " + LeakyReLU", {seg(lat[i], w, "", F, 3, 1)}, F, 2));
+    }
+    for (int i = 0; i < d.downsamples; ++i) {
+      const std::string w = p + "_downsample_layers." + std::to_string(i);
+      lv.push_back(conv(w + " + LeakyReLU", {seg(lv.back(), w, "", F, 3, 2)}, F, 2));
+    }
+    return lv;
+  }
+
+  // x = relu(conv(x) + bn(bottleneck(x))) (prediction_head.py:93-98), n times
+  int blocks(const std::string& lp, const std::string& p, const std::string& g, int n, int x) {
+    for (int i = 0; i < n; ++i) {
+      const std::string is = std::to_string(i);
+      const std::string b = p + g + "_layers." + is;
+      const int t1 = conv(lp + b + ".conv1", {seg(x, b + ".conv1", b + ".bn1", F, 1, 1)}, F / 4, 1);
+      const int t2 = conv(lp + b + ".conv2", {seg(t1, b + ".conv2", b + ".bn2", F / 4, 3, 1)}, F / 4, 1);
+      const int y = conv(lp + b + ".conv3 + x", {seg(t2, b + ".conv3", b + ".bn3", F / 4, 1, 1), identity(x, F, "")}, F, 1);
+      const std::string c = p + g + "_conv_layers." + is;
+      x = conv(lp + c + " + " + g + "_bn_layers." + is + "(bottleneck)",
+               {seg(x, c, "", F, 1, 1), identity(y, F, p + g + "_bn_layers." + is)}, F, 1);
+    }
+    return x;
+  }
+
+  // a final 3x3 conv (or the three stacked along N) into an fp32 raw tensor
+  int final_conv(const std::string& label, int x, const std::vector<std::string>& names, const std::vector<int>& ns) {
+    const TensorSpec t = P.tensors[x];
+    int n = 0;
+    for (int v : ns) n += v;
+    OpSpec op;
+    op.kind = OP_CONV;
+    op.label = label;
+    op.segs = {SegSpec{x, "", "", 0, F, 3, 3, 1, 1}};
+    op.stack_w = names;
+    op.stack_n = ns;
+    op.N = (n + 3) / 4 * 4;  // the fp32 store writes whole 16-byte vectors: zero weight rows up to it
+    op.act = 0;
+    op.out_f32 = true;
+    op.flops = 2.0 * t.H * t.W * n * 9.0 * F;
+    op.out = tensor(t.H, t.W, op.N, true);
+    P.ops.push_back(op);
+    return op.out;
+  }
+
+  void run() {
+    const std::string fp = head ? "_feature_pyramid." : "";
+    fpn_params(fp);
+    const std::vector<int> lv = fpn(fp);
+    if (!head) {
+      for (size_t l = 0; l < lv.size(); ++l) {  // each level into the caller's fp32 NHWC buffer: an identity 1x1 GEMM
+        const TensorSpec t = P.tensors[lv[l]];
+        OpSpec o;
+        o.kind = OP_CONV;
+        o.label = "fpn[" + std::to_string(l) + "] -> fp32 NHWC";
+        o.segs = {identity(lv[l], F, "")};
+        o.N = F;
+        o.act = 0;
+        o.out = -1 - (int)l;
+        P.outs.push_back(IoSpec{t.H, t.W, F, F});
+        P.ops.push_back(o);
+      }
+      return;
+    }
+    const int k = d.head_channels[0], C1 = d.head_channels[1] + 1, nar = d.n_aspect_ratios;
+    int A = 0;
+    for (int t : lv) A += P.tensors[t].H * P.tensors[t].W * nar;
+    P.outs = {IoSpec{A, 1, C1, C1}, IoSpec{A, 1, 4, 4}, IoSpec{A, 1, k, k}, IoSpec{}};
+    P.outs[3] = append_protonet(P, "_masknet.", lv[0], F, k, 3);
+    const std::string hp = "_prediction_head.";
+    group_params(hp, "_extra", d.heights[0]);
+    group_params(hp, "_classification_extra", d.heights[1]);
+    group_params(hp, "_box_extra", d.heights[2]);
+    group_params(hp, "_mask_extra", d.heights[3]);
+    const std::vector<std::string> fin{hp + "_classification_layer", hp + "_box_encoding_layer", hp + "_mask_coeff_layer"};
+    const std::vector<int> width{C1, 4, k};
+    for (int j = 0; j < 3; ++j) conv_p(fin[j], nar * width[j], F, 3);
+    const bool stacked = !d.heights[1] && !d.heights[2] && !d.heights[3];
+    int row0 = 0;
+    for (size_t l = 0; l < lv.size(); ++l) {
+      const std::string lp = "level " + std::to_string(l) + " ";
+      const TensorSpec t = P.tensors[lv[l]];
+      const int x = blocks(lp, hp, "_extra", d.heights[0], lv[l]);
+      OpSpec sc;
+      sc.kind = OP_HEAD_SCATTER;
+      sc.label = lp + "raw heads -> classification / box_encoding / tanh(mask_coeff)";
+      sc.out = -1;
+      sc.N = 0;
+      sc.act = 0;
+      if (stacked) {
+        const int raw = final_conv(lp + "final 3x3 convs (stacked)", x, fin, {nar * C1, nar * 4, nar * k});
+        int c0 = 0;
+        for (int j = 0; j < 3; ++j) {
+          sc.parts.push_back(ScatterPart{raw, c0, nar * width[j], j, row0, width[j], j == 2});
+          c0 += nar * width[j];
+        }
+      } else {
+        const char* g[3] = {"_classification_extra", "_box_extra", "_mask_extra"};
+        for (int j = 0; j < 3; ++j) {
+          const int xb = blocks(lp, hp, g[j], d.heights[1 + j], x);
+          const int raw = final_conv(lp + fin[j], xb, {fin[j]}, {nar * width[j]});
+          sc.parts.push_back(ScatterPart{raw, 0, nar * width[j], j, row0, width[j], j == 2});
+        }
+      }
+      P.ops.push_back(sc);
+      row0 += t.H * t.W * nar;
+    }
+  }
+};
+
+}  // namespace
+
+int build_plan_yolact_head(const tv_model_desc& d, Plan* plan) {
+  const bool head = d.arch == TV_ARCH_YOLACT_HEAD;
+  if (d.compute_dtype < 0 || d.compute_dtype > 2 || d.n_levels < 1 || d.downsamples < 0 ||
+      d.n_levels + d.downsamples > kMaxIO) {
+    set_error("yolact head desc: need 1..8 backbone maps and FPN levels in all");
+    return TV_EINVAL;
+  }
+  if (d.n_maps != d.n_levels) {
+    set_error("yolact head desc: " + std::to_string(d.n_maps) + " map sizes for " + std::to_string(d.n_levels) +
+              " backbone maps");
+    return TV_EINVAL;
+  }
+  const int vec = 16 / dtype_size(d.compute_dtype);
+  const int F = d.channels[0];
+  for (int i = 0; i <= d.n_levels; ++i)
+    if (d.channels[i] < 1 || d.channels[i] % vec) {
+      set_error("yolact head desc: feature_depth and the backbone depths must be multiples of " + std::to_string(vec) +
+                " for this dtype");
+      return TV_ESHAPE;
+    }
+  for (int i = 0; i < d.n_levels; ++i)
+    if (d.map_h[i] < 1 || d.map_w[i] < 1) {
+      set_error("yolact head desc: map sizes must be positive");
+      return TV_EINVAL;
+    }
+  if (head) {
+    if (d.n_aspect_ratios < 1) {
+      set_error("yolact head desc: need at least one anchor aspect ratio");
+      return TV_EINVAL;
+    }
+    bool any = false, ok = d.n_heads == 2 && d.head_channels[0] >= 1 && d.head_channels[1] >= 1;
+    for (int j = 0; j < 4; ++j) {
+      ok = ok && d.heights[j] >= 0 && d.heights[j] <= 8;
+      any = any || d.heights[j] > 0;
+    }
+    if (!ok) {
+      set_error("yolact head desc: need head_channels = (n_prototype_masks, n_classes) and four layer counts in 0..8");
+      return TV_EINVAL;
+    }
+    if (any && (F % 4 || (F / 4) % vec)) {
+      set_error("yolact head desc: the Bottleneck width feature_depth / 4 must be a multiple of " + std::to_string(vec) +
+                " for this dtype");
+      return TV_ESHAPE;
+    }
+  }
+  *plan = Plan();
+  HeadWalker w{d, *plan, F, head};
+  w.run();
+  for (const ParamInfo& p : plan->params) plan->names.insert(p.name);
+  for (auto& op : plan->ops) plan->flops_per_frame += op.flops;
+  plan->in_channels = d.channels[1];
+  return TV_OK;
+}
+
+}  // namespace tv

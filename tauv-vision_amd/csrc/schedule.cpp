@@ -90,6 +90,8 @@ struct Planner {
         case OP_MAXPOOL: kind(i) = Route::MaxPool; break;
         case OP_DCN: kind(i) = dcn_fusable(i) ? Route::DcnInFused : Route::DcnSample; break;
         case OP_DWCONVT_ADD: kind(i) = Route::DwConvTAdd; break;
+        case OP_BILINEAR_ADD: kind(i) = Route::BilinearAdd; break;
+        case OP_HEAD_SCATTER: kind(i) = Route::HeadScatter; break;
       }
     }
     if (e.stem_op >= 0) kind(e.stem_op) = e.ss2_op >= 0 ? Route::StemInS2 : Route::Stem;
@@ -107,6 +109,7 @@ struct Planner {
       auto used = [&](int t) { if (t >= 0) last[t] = std::max(last[t], ws.level[i]); };
       for (int t : {op.out, op.out2, op.src, op.add}) used(t);
       for (const SegSpec& s : op.segs) used(s.src);
+      for (const ScatterPart& q : op.parts) used(q.src);
       // the fused DCNv2 kernel (dcn.hip) samples x and reads the offset / mask tensor while it runs
       // the column GEMM (op i): both stay live through it
       if (op.kind == OP_CONV && i > 0 && plan.ops[i - 1].kind == OP_DCN && op.segs.size() == 1 &&
@@ -122,7 +125,7 @@ struct Planner {
       if (placed[tid]) return;
       placed[tid] = 1;
       const TensorSpec& t = plan.tensors[tid];
-      size_t sz = align_up((size_t)B * t.H * t.W * t.C * esz, 256);
+      size_t sz = align_up((size_t)B * t.H * t.W * t.C * (t.f32 ? 4 : esz), 256);
       std::sort(live.begin(), live.end(), [](const Live& a, const Live& b) { return a.off < b.off; });
       size_t pos = 0;
       for (const Live& l : live) {
@@ -164,11 +167,11 @@ struct Planner {
                                  sg.pad_w >= 0 ? sg.pad_w : sg.pad, pk.seg_ksteps[s], kbase};
           kbase += pk.seg_ksteps[s];
         }
-        p.Ho = op.up_s ? op.gh : op.out >= 0 ? plan.tensors[op.out].H : plan.out_h;
-        p.Wo = op.up_s ? op.gw : op.out >= 0 ? plan.tensors[op.out].W : plan.out_w;
+        p.Ho = op.up_s ? op.gh : op.out >= 0 ? plan.tensors[op.out].H : plan.outspec(op.out).H;
+        p.Wo = op.up_s ? op.gw : op.out >= 0 ? plan.tensors[op.out].W : plan.outspec(op.out).W;
         p.N = op.N;
         p.out = op.out >= 0 ? at(op.out) : nullptr;  // the caller's fp32 output: patched per call
-        p.out_ldc = op.out >= 0 ? plan.tensors[op.out].C : plan.out_cpad;
+        p.out_ldc = op.out >= 0 ? plan.tensors[op.out].C : plan.outspec(op.out).cpad;
         p.ntiles = pk.Npad / kTile;
       } else {
         const TensorSpec& src = plan.tensors[op.src];
@@ -250,7 +253,7 @@ struct Planner {
     for (size_t i = 0; e.conv3_mode && dtype != F32 && i < nops; ++i) {
       const OpSpec& op = plan.ops[i];
       ConvParams& p = ws.params[i];
-      if (!generic(i) || op.kind != OP_CONV || op.out < 0 || op.add >= 0) continue;
+      if (!generic(i) || op.kind != OP_CONV || op.out < 0 || op.out_f32 || op.add >= 0) continue;
       const bool res2 = op.segs.size() == 2 && op.segs[1].kh == 1 && op.segs[1].kw == 1 && op.segs[1].pad == 0 &&
                         p.seg[1].C <= p.seg[0].C && p.seg[1].C % 32 == 0 && p.seg[1].ldc % 8 == 0 && op.act == 1 &&
                         (size_t)p.seg[1].H * p.seg[1].W * p.seg[1].ldc * esz < (1ull << 31) &&
@@ -312,7 +315,7 @@ struct Planner {
     for (size_t i = 0; e.s2_mode && dtype != F32 && i < nops; ++i) {
       const OpSpec& op = plan.ops[i];
       ConvParams& p = ws.params[i];
-      if (!generic(i) || op.kind != OP_CONV || op.segs.size() != 1 || op.out < 0 || op.add >= 0) continue;
+      if (!generic(i) || op.kind != OP_CONV || op.segs.size() != 1 || op.out < 0 || op.out_f32 || op.add >= 0) continue;
       const SegSpec& sg = op.segs[0];
       const ConvSegment& cs = p.seg[0];
       const int pw = sg.pad_w >= 0 ? sg.pad_w : sg.pad;
@@ -334,7 +337,8 @@ struct Planner {
   void pass_conv_small() {
     for (size_t i = 0; dtype != F32 && i < nops; ++i) {
       const OpSpec& op = plan.ops[i];
-      if (!generic(i) || op.kind != OP_CONV || op.segs.size() != 1 || op.out < 0 || op.add >= 0 || op.up_s) continue;
+      if (!generic(i) || op.kind != OP_CONV || op.segs.size() != 1 || op.out < 0 || op.out_f32 || op.add >= 0 || op.up_s)
+        continue;
       const SegSpec& sg = op.segs[0];
       const ConvParams& p = ws.params[i];
       if (sg.kh == 3 && sg.kw == 3 && sg.pad == 1 && (sg.pad_w < 0 || sg.pad_w == 1) && !sg.row_expand &&
@@ -391,18 +395,19 @@ struct Planner {
           h2.out >= 0 || h2.segs[0].src != h1.out || p.ntiles != h1.N / 128 ||
           (h1.act != 2 && !(h1.act == 1 && plan.tensors[h1.segs[0].src].C == 64)))
         continue;
-      p.head_ldc = plan.out_cpad;
+      const int out_cpad = plan.outspec(h2.out).cpad;
+      p.head_ldc = out_cpad;
       for (int t = 0; t < 16; ++t) p.head_row0[t] = pk2.head_row0[t], p.head_nrows[t] = pk2.head_nrows[t];
       // plain stores when the tiles' head rows tile the output columns exactly once (one 128-channel
       // hidden tile per head: a 64-channel backbone's 2C heads); otherwise (a head's 2C = 256 hidden
       // channels, centernet.py:45-50 on the 128-channel "R18" and DLA-34, span two tiles that meet in
       // the output) atomics onto a zeroed output
-      std::vector<int> cover(plan.out_cpad, 0);
+      std::vector<int> cover(out_cpad, 0);
       bool ok = true;
       for (int t = 0; t < p.ntiles && t < 16; ++t)
         for (int r = 0; r < p.head_nrows[t]; ++r) {
           const int c = p.head_row0[t] + r;
-          if (c < 0 || c >= plan.out_cpad) ok = false;
+          if (c < 0 || c >= out_cpad) ok = false;
           else ++cover[c];
         }
       for (int c : cover) ok = ok && c == 1;
@@ -474,7 +479,7 @@ struct Planner {
       const OpSpec& op = plan.ops[i];
       ConvParams& p = ws.params[i];
       const bool c3 = kind(i) == Route::Conv3x3, s2 = kind(i) == Route::Conv3x3S2;
-      if (!(generic(i) || c3 || s2) || op.kind != OP_CONV || op.up_s || op.out < 0 || op.add >= 0 || !lat_ok[i] ||
+      if (!(generic(i) || c3 || s2) || op.kind != OP_CONV || op.up_s || op.out < 0 || op.out_f32 || op.add >= 0 || !lat_ok[i] ||
           p.N % 8 || p.out_ldc % 8 || p.out_coff % 8)
         continue;
       long units = 0;  // conv_igemm corner case: always worse than conv_lat
@@ -525,7 +530,7 @@ struct Planner {
   void pass_conv1x1() {
     for (size_t i = 0; e.c1x1_mode && dtype != F32 && i < nops; ++i) {
       const OpSpec& op = plan.ops[i];
-      if (!generic(i) || op.kind != OP_CONV || op.up_s || op.add >= 0 || op.out < 0) continue;
+      if (!generic(i) || op.kind != OP_CONV || op.up_s || op.add >= 0 || op.out < 0 || op.out_f32) continue;
       bool one = !op.segs.empty();
       for (const SegSpec& sg : op.segs)
         one = one && sg.kh == 1 && sg.kw == 1 && sg.stride == 1 && sg.pad == 0 && !sg.row_expand && sg.convt_phase < 0;

@@ -19,7 +19,10 @@ c_i32, c_i64, c_f32, c_f64, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_floa
 class ModelDesc(ctypes.Structure):
     _fields_ = [("n_levels", c_i32), ("heights", c_i32 * 8), ("channels", c_i32 * 9), ("downsamples", c_i32),
                 ("n_heads", c_i32), ("head_channels", c_i32 * 16), ("in_h", c_i32), ("in_w", c_i32),
-                ("compute_dtype", c_i32), ("arch", c_i32)]
+                ("compute_dtype", c_i32), ("arch", c_i32),
+                # ARCH_YOLACT_HEAD / ARCH_YOLACT_FPN only (zero otherwise): the backbone maps' sizes, the
+                # aspect-ratio count (the encoding of the other fields: include/tauv_vision_amd.h)
+                ("n_maps", c_i32), ("map_h", c_i32 * 8), ("map_w", c_i32 * 8), ("n_aspect_ratios", c_i32)]
 
 
 class WeightView(ctypes.Structure):
@@ -32,6 +35,12 @@ EXPORTS = {
                              ctypes.POINTER(c_i32)], c_i32),
     "tv_model_geometry": ([ctypes.POINTER(ModelDesc), ctypes.POINTER(c_f64), ctypes.POINTER(c_i32),
                            ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)], c_i32),
+    "tv_model_io": ([ctypes.POINTER(ModelDesc), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32 * 3), ctypes.POINTER(c_i32),
+                     ctypes.POINTER(c_i32 * 4)], c_i32),
+    "tv_engine_forward_multi": ([c_vp, ctypes.POINTER(c_vp), c_i32, ctypes.POINTER(c_vp), c_i32, c_i32, c_vp], c_i32),
+    "tv_engine_profile_multi": ([c_vp, ctypes.POINTER(c_vp), c_i32, ctypes.POINTER(c_vp), c_i32, c_i32, c_vp,
+                                 ctypes.POINTER(c_f32), ctypes.POINTER(c_f64), c_i32, ctypes.POINTER(c_i32)], c_i32),
+    "tv_diag_bilinear_add": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp], c_i32),
     "tv_engine_create": ([ctypes.POINTER(ModelDesc), ctypes.POINTER(WeightView), c_i32, c_i32,
                           ctypes.POINTER(c_vp)], c_i32),
     "tv_engine_create_diag": ([ctypes.POINTER(ModelDesc), ctypes.POINTER(WeightView), c_i32, c_i32,

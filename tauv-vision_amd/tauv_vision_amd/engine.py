@@ -95,6 +95,33 @@ class NativeEngine:
                    "forward")
         return out
 
+    @staticmethod
+    def _ptrs(tensors):
+        return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+    def forward_multi(self, inputs, outputs):
+        """An arch with several inputs and outputs (weights.model_io): `inputs` contiguous fp32 NCHW
+        and `outputs` contiguous fp32 tensors on this device, all of one batch size, checked by the
+        caller — the library reads and writes through their raw pointers."""
+        B = inputs[0].shape[0]
+        if B == 0:
+            return outputs
+        _lib.check(_lib.lib().tv_engine_forward_multi(self._h, self._ptrs(inputs), len(inputs), self._ptrs(outputs),
+                                                      len(outputs), B, _lib.stream_of(self.device)), "forward")
+        return outputs
+
+    def profile_multi(self, inputs, outputs, cap=4096):
+        """profile() over the buffers of forward_multi."""
+        B = inputs[0].shape[0]
+        ms = (ctypes.c_float * cap)()
+        fl = (ctypes.c_double * cap)()
+        n = ctypes.c_int32()
+        L = _lib.lib()
+        _lib.check(L.tv_engine_profile_multi(self._h, self._ptrs(inputs), len(inputs), self._ptrs(outputs), len(outputs),
+                                             B, _lib.stream_of(self.device), ms, fl, cap, ctypes.byref(n)), "profile")
+        return [(L.tv_engine_op_label(self._h, i).decode(), ms[i], fl[i], L.tv_engine_op_kernel(self._h, B, i).decode())
+                for i in range(min(n.value, cap))]
+
     def forward_u8(self, frames, out=None):
         """frames: uint8 NHWC RGB on this device (ToTensor + ImageNet Normalize fused)."""
         B = frames.shape[0]

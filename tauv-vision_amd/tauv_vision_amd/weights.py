@@ -8,7 +8,7 @@ import torch
 from . import _lib
 
 
-ARCH_CENTERNET, ARCH_DLA34, ARCH_PROTONET, ARCH_CENTERNET_BACKBONE = 0, 1, 2, 3
+ARCH_CENTERNET, ARCH_DLA34, ARCH_PROTONET, ARCH_CENTERNET_BACKBONE, ARCH_YOLACT_HEAD, ARCH_YOLACT_FPN = range(6)
 
 
 def model_desc(heights, channels, downsamples, head_channels, in_h=64, in_w=64, precision="fp32",
@@ -43,6 +43,40 @@ def dla34_desc(head_channels, in_h=64, in_w=64, precision="fp32"):
 def protonet_desc(feature_depth, n_prototype_masks, fpn_h=8, fpn_w=8, precision="fp32"):
     """YOLACT Masknet (masknet.py:8-55) over an fpn[0] map of fpn_h x fpn_w."""
     return model_desc([], [feature_depth], 0, [n_prototype_masks], fpn_h, fpn_w, precision, arch=ARCH_PROTONET)
+
+
+def yolact_head_desc(in_depths, map_sizes, feature_depth, n_fpn_downsample_layers, n_classes=0, n_prototype_masks=0,
+                     n_aspect_ratios=0, layers=(0, 0, 0, 0), precision="fp32", fpn_only=False):
+    """Everything of Yolact.forward after the backbone (ARCH_YOLACT_HEAD) or its FeaturePyramid alone
+    (fpn_only: ARCH_YOLACT_FPN) over backbone maps of `in_depths` channels and `map_sizes` [(h, w)].
+    `layers` = (n_prediction_head_layers, n_classification_layers, n_box_layers, n_mask_layers).
+    The field encoding is documented at tv_model_desc in include/tauv_vision_amd.h."""
+    if len(in_depths) > 8 or len(map_sizes) > 8 or len(layers) != 4:
+        raise ValueError("at most 8 backbone maps; four layer counts")
+    heads = [] if fpn_only else [n_prototype_masks, n_classes]
+    d = model_desc(list(layers), [feature_depth] * 5, n_fpn_downsample_layers, heads, 0, 0, precision,
+                   arch=ARCH_YOLACT_FPN if fpn_only else ARCH_YOLACT_HEAD)
+    d.n_levels = len(in_depths)
+    for i in range(9):
+        d.channels[i] = 0
+    d.channels[0] = int(feature_depth)
+    for i, c in enumerate(in_depths):
+        d.channels[1 + i] = int(c)
+    d.n_maps = len(map_sizes)
+    for i, (h, w) in enumerate(map_sizes):
+        d.map_h[i], d.map_w[i] = int(h), int(w)
+    d.n_aspect_ratios = int(n_aspect_ratios)
+    return d
+
+
+def model_io(desc):
+    """The caller's buffers of a desc, per frame: ([(C, H, W)] of the fp32 NCHW inputs,
+    [(H, W, C, cpad)] of the fp32 NHWC outputs)."""
+    n_in, n_out = ctypes.c_int32(), ctypes.c_int32()
+    ins, outs = ((ctypes.c_int32 * 3) * 8)(), ((ctypes.c_int32 * 4) * 8)()
+    _lib.check(_lib.lib().tv_model_io(ctypes.byref(desc), ctypes.byref(n_in), ins, ctypes.byref(n_out), outs),
+               "model io")
+    return [tuple(ins[i]) for i in range(n_in.value)], [tuple(outs[i]) for i in range(n_out.value)]
 
 
 def param_layout(desc):

@@ -19,7 +19,7 @@ import torch.nn as nn
 from . import _lib
 from .dla import populate
 from .engine import NativeEngine
-from .weights import param_layout, protonet_desc
+from .weights import model_io, param_layout, protonet_desc, yolact_head_desc
 
 
 @dataclass
@@ -33,6 +33,24 @@ class YolactConfig:
     box_variances: Tuple[float, float]
     feature_depth: int = 256
     n_prototype_masks: int = 8
+    # read by the neck and the head (FeaturePyramid, PredictionHead, YolactHead)
+    n_classes: int = 1
+    n_prediction_head_layers: int = 1
+    n_classification_layers: int = 0
+    n_box_layers: int = 0
+    n_mask_layers: int = 0
+    n_fpn_downsample_layers: int = 2
+
+
+def _head_layers(config):
+    return (int(config.n_prediction_head_layers), int(config.n_classification_layers), int(config.n_box_layers),
+            int(config.n_mask_layers))
+
+
+def _head_desc(in_depths, sizes, config, precision, fpn_only=False):
+    return yolact_head_desc(in_depths, sizes, int(config.feature_depth), int(config.n_fpn_downsample_layers),
+                            int(config.n_classes), int(config.n_prototype_masks), len(config.anchor_aspect_ratios),
+                            _head_layers(config), precision, fpn_only)
 
 
 class Masknet(nn.Module):
@@ -300,3 +318,226 @@ def assemble_masks_indexed(mask_prototype: torch.Tensor, mask_coeff: torch.Tenso
         A, ctypes.c_void_p(det.data_ptr()), ctypes.c_void_p(counts.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
         _lib.stream_of(proto.device)), "assemble_masks_indexed")
     return out
+
+
+# ---- the neck and the head: everything of Yolact.forward after the backbone (model.py:34-60) ----
+
+def yolact_head_state_dict(state_dict):
+    """A reference Yolact state_dict without its `_backbone.*` entries: what YolactHead.load_state_dict
+    takes (`_feature_pyramid.*`, `_masknet.*`, `_prediction_head.*`)."""
+    return {k: v for k, v in state_dict.items() if not k.startswith("_backbone.")}
+
+
+class _NativeNet(nn.Module):
+    """Reference-layout parameters + the cache of native engines built from them (one per device,
+    map sizes and precision), dropped whenever the parameters may have changed."""
+
+    def _init_native(self, precision):
+        if precision not in _lib.DTYPES:
+            raise ValueError(f"precision must be one of {sorted(_lib.DTYPES)}")
+        self.precision = precision
+        self._version = 0
+        self._engines = {}
+        self.register_load_state_dict_post_hook(lambda module, keys: module.invalidate())
+
+    def invalidate(self):
+        self._version += 1
+        self._engines = {}
+
+    def _apply(self, fn, *args, **kwargs):
+        r = super()._apply(fn, *args, **kwargs)
+        self.invalidate()
+        return r
+
+    def _maps(self, backbone_outputs, in_depths):
+        """The backbone maps as contiguous fp32 NCHW tensors of one CUDA device and batch; refuses
+        anything else before a launch."""
+        maps = tuple(backbone_outputs)
+        if len(maps) != len(in_depths):
+            raise ValueError(f"expected {len(in_depths)} backbone maps, got {len(maps)}")
+        if not torch.cuda.is_available():
+            raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
+        dev, B = maps[0].device, maps[0].shape[0]
+        out = []
+        for i, (m, c) in enumerate(zip(maps, in_depths)):
+            if m.dim() != 4 or m.shape[1] != c or m.shape[0] != B:
+                raise ValueError(f"backbone map {i}: expected [{B}, {c}, H, W], got {tuple(m.shape)}")
+            if m.device != dev or not m.is_cuda:
+                raise ValueError(f"backbone map {i} is on {m.device}; every map must be on one CUDA device "
+                                 f"(map 0 is on {dev})")
+            out.append(m.to(torch.float32).contiguous())
+        return out
+
+    def _engine(self, key, make_desc, state_dict):
+        key = key + (self.precision, self._version_key())
+        eng = self._engines.get(key)
+        if eng is None:
+            eng = NativeEngine(make_desc(), state_dict(), key[0])
+            self._engines = {key: eng}
+        return eng
+
+    def _version_key(self):
+        return self._version
+
+
+def _outputs(out, shapes, device, what):
+    """Caller-owned output buffers (or fresh ones): contiguous fp32 of exactly `shapes` on `device`."""
+    if out is None:
+        return [torch.empty(s, dtype=torch.float32, device=device) for s in shapes]
+    out = list(out)
+    if len(out) != len(shapes):
+        raise ValueError(f"{what}: out must hold {len(shapes)} tensors, got {len(out)}")
+    return [_check_out(o, s, device, f"{what} out[{i}]") for i, (o, s) in enumerate(zip(out, shapes))]
+
+
+class FeaturePyramid(_NativeNet):
+    """feature_pyramid.py:8-58: the backbone maps (c3, c4, c5) -> the tuple of len(in_depths) +
+    n_fpn_downsample_layers maps [B, F, h, w]. Parameters keep the reference keys
+    (`_lateral_layers.i.*`, `_downsample_layers.i.*`, `_prediction_layers.i.*`). One native call:
+    lateral 1x1 convs, the top-down bilinear up-sampling + add in place (any per-axis ratio, as
+    F.interpolate(mode="bilinear")), 3x3 convs + LeakyReLU. Each result is a [B, F, h, w] view of an
+    fp32 NHWC tensor; `out`: caller-owned NHWC buffers [B, h, w, F]."""
+
+    def __init__(self, in_depths, config, precision: str = "fp32"):
+        super().__init__()
+        self.in_depths = tuple(int(c) for c in in_depths)
+        self.config = config
+        self._init_native(precision)
+        layout = param_layout(_head_desc(self.in_depths, [(1, 1)] * len(self.in_depths), config, "fp32", True))
+        populate(self, layout, seed_layout=layout)
+
+    def forward_nhwc(self, backbone_outputs, out=None):
+        maps = self._maps(backbone_outputs, self.in_depths)
+        sizes = tuple((m.shape[2], m.shape[3]) for m in maps)
+        dev = maps[0].device
+        eng = self._engine((dev.index, sizes), lambda: _head_desc(self.in_depths, sizes, self.config, self.precision, True),
+                           self.state_dict)
+        B = maps[0].shape[0]
+        outs = _outputs(out, [(B, h, w, cp) for h, w, _, cp in model_io(eng.desc)[1]], dev, "FeaturePyramid")
+        eng.forward_multi(maps, outs)
+        return tuple(outs)
+
+    def forward(self, backbone_outputs, out=None):
+        return tuple(o.permute(0, 3, 1, 2) for o in self.forward_nhwc(backbone_outputs, out))
+
+
+class PredictionHead(_NativeNet):
+    """prediction_head.py:9-143: the parameters of the one head shared by every FPN level, in the
+    reference layout (the Bottleneck blocks as torchvision's: conv1, bn1, conv2, bn2, conv3, bn3,
+    bias-free convs). It runs inside YolactHead's native plan, once per level with the same weights;
+    on its own it has no forward."""
+
+    def __init__(self, config, precision: str = "fp32"):
+        super().__init__()
+        self.config = config
+        self._init_native(precision)
+        F = int(config.feature_depth)
+        layout = [(k[len("_prediction_head."):], s) for k, s in param_layout(_head_desc((F,), [(1, 1)], config, "fp32"))
+                  if k.startswith("_prediction_head.")]
+        populate(self, layout, seed_layout=layout)
+
+    def forward(self, fpn_output):
+        raise RuntimeError("PredictionHead runs inside YolactHead's native plan (one launch sequence for the "
+                           "neck, every level's head and the protonet); call YolactHead((c3, c4, c5))")
+
+
+class YolactHead(_NativeNet):
+    """Everything of Yolact.forward after the backbone (model.py:34-60): (c3, c4, c5) ->
+    (classification [B, A, C+1], box_encoding [B, A, 4], mask_coeff [B, A, k], anchor [1, A, 4],
+    mask_prototype [B, k, 4h, 4w]), all fp32, in one native call. The three anchor-indexed tensors are
+    contiguous; mask_prototype is a view of an fp32 NHWC tensor (Masknet's layout).
+
+    Sub-modules `_feature_pyramid`, `_masknet`, `_prediction_head` are the reference Yolact's
+    attributes, so `load_state_dict(yolact_head_state_dict(reference_yolact.state_dict()))` works.
+    Two reference quirks are kept: one PredictionHead for every level, and rows ordered pixel-major
+    with the aspect ratio innermost ((y * W + x) * n_ar + a, prediction_head.py:112-113) while
+    get_anchor lays its anchors out one block per aspect ratio.
+
+    `out`: caller-owned (classification, box_encoding, mask_coeff, mask_prototype NHWC [B, 4h, 4w, k
+    rounded up to 4]) buffers — with them a step allocates nothing and can be captured in a graph
+    after one eager call on the capture stream.
+
+    Only this module's `precision` counts for its forward (`set_precision` changes it); the
+    sub-modules hold the parameters."""
+
+    def __init__(self, in_depths, config, precision: str = "fp32"):
+        super().__init__()
+        self.in_depths = tuple(int(c) for c in in_depths)
+        self.config = config
+        self._init_native(precision)
+        self._feature_pyramid = FeaturePyramid(self.in_depths, config, precision)
+        self._masknet = Masknet(config, precision)
+        self._prediction_head = PredictionHead(config, precision)
+        self._anchors = {}
+
+    def set_precision(self, precision: str):
+        """The head's one precision. The sub-modules are used here as parameter holders: their own
+        `precision` and engine caches serve only a direct call of `_feature_pyramid(...)` or
+        `_masknet(...)`, never this module's forward; they are kept equal to the head's."""
+        if precision not in _lib.DTYPES:
+            raise ValueError(f"precision must be one of {sorted(_lib.DTYPES)}")
+        for m in (self, self._feature_pyramid, self._masknet, self._prediction_head):
+            m.precision = precision
+            m.invalidate()
+
+    def _version_key(self):
+        return (self._version, self._feature_pyramid._version, self._masknet._version, self._prediction_head._version)
+
+    def head_state_dict(self):
+        return yolact_head_state_dict(self.state_dict())
+
+    def anchor(self, level_sizes, device):
+        """torch.cat of get_anchor over the FPN levels (model.py:47-58), [1, A, 4], cached."""
+        key = (tuple(level_sizes), device)
+        a = self._anchors.get(key)
+        if a is None:
+            a = torch.cat([get_anchor(i, s, self.config) for i, s in enumerate(level_sizes)], dim=1)
+            self._anchors = {key: a.to(device, torch.float32).contiguous()}
+            a = self._anchors[key]
+        return a
+
+    def level_sizes(self, sizes):
+        """(h, w) of every FPN level for backbone maps of `sizes`."""
+        out = [tuple(int(v) for v in s) for s in sizes]
+        for _ in range(int(self.config.n_fpn_downsample_layers)):
+            out.append(((out[-1][0] - 1) // 2 + 1, (out[-1][1] - 1) // 2 + 1))
+        return out
+
+    def engine(self, device, sizes):
+        return self._engine((device.index, tuple(sizes)),
+                            lambda: _head_desc(self.in_depths, sizes, self.config, self.precision), self.head_state_dict)
+
+    def forward(self, backbone_outputs, out=None):
+        maps = self._maps(backbone_outputs, self.in_depths)
+        sizes = tuple((m.shape[2], m.shape[3]) for m in maps)
+        levels = self.level_sizes(sizes)
+        if len(levels) > len(self.config.anchor_scales):
+            raise ValueError(f"{len(levels)} FPN levels but {len(self.config.anchor_scales)} anchor_scales")
+        dev = maps[0].device
+        eng = self.engine(dev, sizes)
+        B = maps[0].shape[0]
+        (A, _, c1, _), _, (_, _, k, _), (ph, pw, _, kp) = model_io(eng.desc)[1]
+        outs = _outputs(out, [(B, A, c1), (B, A, 4), (B, A, k), (B, ph, pw, kp)], dev, "YolactHead")
+        eng.forward_multi(maps, outs)
+        return outs[0], outs[1], outs[2], self.anchor(levels, dev), outs[3][..., :k].permute(0, 3, 1, 2)
+
+
+class Yolact(YolactHead):
+    """model.py:18-60 with the caller's backbone: `backbone(img)` -> the three maps (any nn.Module,
+    e.g. a torchvision feature extractor under PyTorch-ROCm; `in_depths` defaults to its `depths`
+    attribute, else the reference backbone's (128, 256, 512)), then YolactHead. A reference Yolact
+    state_dict loads as a whole when the backbone has the reference's parameter names."""
+
+    def __init__(self, config, backbone: Optional[nn.Module] = None, precision: str = "fp32", in_depths=None):
+        if in_depths is None:
+            in_depths = getattr(backbone, "depths", (128, 256, 512))
+        super().__init__(in_depths, config, precision)
+        if backbone is not None:
+            self._backbone = backbone
+
+    def forward(self, img, out=None):
+        if getattr(self, "_backbone", None) is None:
+            raise RuntimeError("Yolact was built without a backbone: the ResNet is not part of this library. Pass "
+                               "backbone=<nn.Module returning (c3, c4, c5)>, or run your backbone yourself and call "
+                               "YolactHead((c3, c4, c5))")
+        return super().forward(self._backbone(img), out)
