@@ -198,6 +198,23 @@ const char* tv_engine_op_label(tv_engine* engine, int32_t index);
  * inside another op's launch, e.g. "(fused into the 3x3 heads)". "" before the batch's workspace
  * exists or past the last op. Diagnostic (roofline attribution, route table test). */
 const char* tv_engine_op_kernel(tv_engine* engine, int32_t batch, int32_t index);
+/* Diagnostic (per-layer tests): what op i < *n_ops of the `batch`-frame workspace on `stream` stores,
+ * shape[i] = (H, W, C, element bytes) of its NHWC [batch, H, W, C] output tensor as stored (compute
+ * dtype, 4 bytes for fp32 tensors; the op that writes the caller's output reports that buffer).
+ * All zeros for an op whose output is never stored because another launch does its work: staging
+ * inside the stem, the stem inside stem_s2, the 3x3 heads with the 1x1 heads in their epilogue,
+ * fused DCN sampling, the ConvTranspose phases done by the phase-(0,0) launch. cap entries max.
+ * Makes the workspace if it does not exist (allocates: not inside a stream capture). */
+int tv_engine_op_shapes(tv_engine* engine, int32_t batch, void* stream, int32_t (*shape)[4], int32_t cap,
+                        int32_t* n_ops);
+/* Diagnostic: one forward of `batch` frames as tv_engine_profile runs it (one op per launch in
+ * execution order, no slices) from `input` (input_u8 = 0: normalised fp32 NCHW, 1: u8 NHWC frames);
+ * after op i < n_dst with dst[i] != NULL its stored tensor (tv_engine_op_shapes) is copied to the
+ * device buffer dst[i] on `stream`, before the next op is launched. The data of the op that
+ * writes the caller's output comes from out_nhwc (dst[i] may be out_nhwc itself: no copy). Archs
+ * with one input and one output. Asynchronous like tv_engine_forward. */
+int tv_engine_op_outputs(tv_engine* engine, const void* input, int32_t input_u8, int32_t batch, float* out_nhwc,
+                         void* stream, void* const* dst, int32_t n_dst);
 /* How a forward of `batch` frames is launched: as *n_slices (1..TV_MAX_SLICES) concurrent slices
  * of slice_batch[0..n_slices) frames, the rest of slice_batch zeroed (diagnostic: per-launch
  * roofline attribution). */

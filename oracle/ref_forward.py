@@ -62,23 +62,28 @@ def _bn(sd, p, x):
                         sd[p + ".weight"], sd[p + ".bias"], False, 0.1, 1e-5)
 
 
-def _block(sd, p, x, stride):
+def _tap(hook, label, t):
+    """The layer boundary `label` (the engine's op label): a hook may replace the layer's value."""
+    return t if hook is None else hook(label, t)
+
+
+def _block(sd, p, x, stride, hook=None):
     res = _bn(sd, p + ".bn_residual", _conv(sd, p + ".conv_residual", x, stride))
-    y = F.relu(_bn(sd, p + ".bn1", _conv(sd, p + ".conv1", x, stride, 1)))
+    y = _tap(hook, p + ".conv1", F.relu(_bn(sd, p + ".bn1", _conv(sd, p + ".conv1", x, stride, 1))))
     y = _bn(sd, p + ".bn2", _conv(sd, p + ".conv2", y, 1, 1))
     y += res
-    return F.relu(y)
+    return _tap(hook, p + ".conv2+conv_residual", F.relu(y))
 
 
-def _tree(sd, p, x, height, stride, children=None):
+def _tree(sd, p, x, height, stride, children=None, hook=None):
     kids = [] if children is None else children
     if height == 1:
-        left = _block(sd, p + ".tree_l", x, stride)
-        right = _block(sd, p + ".tree_r", left, 1)
+        left = _block(sd, p + ".tree_l", x, stride, hook)
+        right = _block(sd, p + ".tree_r", left, 1, hook)
         cat = torch.cat(kids + [left, right], 1)
-        return F.relu(_bn(sd, p + ".root.bn", _conv(sd, p + ".root.conv", cat)))
-    left = _tree(sd, p + ".tree_l", x, height - 1, stride)
-    return _tree(sd, p + ".tree_r", left, height - 1, 1, kids + [left])
+        return _tap(hook, p + ".root.conv", F.relu(_bn(sd, p + ".root.bn", _conv(sd, p + ".root.conv", cat))))
+    left = _tree(sd, p + ".tree_l", x, height - 1, stride, None, hook)
+    return _tree(sd, p + ".tree_r", left, height - 1, 1, kids + [left], hook)
 
 
 def pad_to_match(feature, shape):
@@ -95,62 +100,80 @@ def pad_to_match(feature, shape):
     return F.pad(feature, (above, below, left, right))[:, :, :th, :tw]
 
 
-def _proj(sd, p, x):
-    return F.relu(_bn(sd, p + ".1", _conv(sd, p + ".0", x, 1, 1)))
+def _proj(sd, p, x, hook=None):
+    return _tap(hook, p + ".0", F.relu(_bn(sd, p + ".1", _conv(sd, p + ".0", x, 1, 1))))
 
 
-def _ida_up(sd, p, feats):
+def _up_add(sd, p, i, x, skip, hook=None):
+    """upsample_layers.i of the projected `x`, pad_to_match, + skip (one engine op)."""
+    up = sd[f"{p}.upsample_layers.{i}.weight"]
+    u = F.conv_transpose2d(_proj(sd, f"{p}.projection_layers.{i}", x, hook), up,
+                           sd[f"{p}.upsample_layers.{i}.bias"], stride=up.shape[2])
+    return _tap(hook, f"{p}.upsample_layers.{i}+pad_to_match+add", skip + pad_to_match(u, skip.shape))
+
+
+def _ida_up(sd, p, feats, hook=None):
     n = len(feats) - 1
     cur = feats[-1]
     outs = []
     for i in reversed(range(n)):
-        up = sd[f"{p}.upsample_layers.{i}.weight"]
-        s = up.shape[2]
-        u = F.conv_transpose2d(_proj(sd, f"{p}.projection_layers.{i}", cur), up,
-                               sd[f"{p}.upsample_layers.{i}.bias"], stride=s)
-        cur = _proj(sd, f"{p}.output_layers.{i}", feats[i] + pad_to_match(u, feats[i].shape))
+        cur = _proj(sd, f"{p}.output_layers.{i}", _up_add(sd, p, i, cur, feats[i], hook), hook)
         outs.append(cur)
     return outs[::-1]
 
 
-def _ida_up_reverse(sd, p, feats):
+def _ida_up_reverse(sd, p, feats, hook=None):
     cur = feats[0]
     for i in range(len(feats) - 1):
-        up = sd[f"{p}.upsample_layers.{i}.weight"]
-        s = up.shape[2]
-        u = F.conv_transpose2d(_proj(sd, f"{p}.projection_layers.{i}", feats[i + 1]), up,
-                               sd[f"{p}.upsample_layers.{i}.bias"], stride=s)
-        cur = _proj(sd, f"{p}.output_layers.{i}", cur + pad_to_match(u, cur.shape))
+        cur = _proj(sd, f"{p}.output_layers.{i}", _up_add(sd, p, i, feats[i + 1], cur, hook), hook)
     return cur
 
 
-def backbone_forward(sd, img, heights, downsamples, prefix="backbone"):
+def backbone_forward(sd, img, heights, downsamples, prefix="backbone", hook=None):
+    """hook(label, tensor) -> tensor, when given, is called at every boundary that is one engine op
+    (label = the engine's op label); the forward goes on from what it returns."""
     p = prefix + ".dla_down"
     x = F.relu(_bn(sd, p + ".projection_layer.1", _conv(sd, p + ".projection_layer.0", img, 1, 3)))
+    x = _tap(hook, p + ".projection_layer.0", x)
     for i in range(downsamples):
-        x = _block(sd, f"{p}.block_layers.{i}", x, 2)
+        x = _block(sd, f"{p}.block_layers.{i}", x, 2, hook)
     feats = [x]
     for i, h in enumerate(heights):
-        x = _tree(sd, f"{p}.tree_layers.{i}", x, h, 2)
+        x = _tree(sd, f"{p}.tree_layers.{i}", x, h, 2, None, hook)
         feats.append(x)
     # MultiIDAUp: IDAUp over a shrinking feature list, keep the last output of each
     collected = []
     for i in range(len(feats) - 1):
-        feats = _ida_up(sd, f"{prefix}.multi_ida_up.ida_up_layers.{i}", feats)
+        feats = _ida_up(sd, f"{prefix}.multi_ida_up.ida_up_layers.{i}", feats, hook)
         collected.append(feats[-1])
     collected = collected[::-1]
-    return _ida_up_reverse(sd, prefix + ".ida_up_reverse", collected)
+    return _ida_up_reverse(sd, prefix + ".ida_up_reverse", collected, hook)
 
 
-def centernet_forward(sd, img, heights, downsamples, flags):
-    """flags: dict(keypoints, yaw, pitch, roll, depth) as in ObjectConfigSet.train_*."""
-    feat = backbone_forward(sd, img, heights, downsamples)
+HEADS_HIDDEN_LABEL = "heads.*.0 (stacked) + LeakyReLU"
+HEADS_OUT_LABEL = "heads.*.2 (block-diagonal) -> fp32 NHWC"
+
+
+def centernet_forward(sd, img, heights, downsamples, flags, hook=None):
+    """flags: dict(keypoints, yaw, pitch, roll, depth) as in ObjectConfigSet.train_*.
+    hook: see backbone_forward; the heads' hidden layers and outputs pass it stacked along the
+    channels in head order, as the engine stores them."""
+    feat = backbone_forward(sd, img, heights, downsamples, hook=hook)
     outs = []
     i = 0
-    while f"heads.{i}.0.weight" in sd:
-        h = F.leaky_relu(F.conv2d(feat, sd[f"heads.{i}.0.weight"], sd[f"heads.{i}.0.bias"], 1, 1))
-        outs.append(F.conv2d(h, sd[f"heads.{i}.2.weight"], sd[f"heads.{i}.2.bias"]))
-        i += 1
+    if hook is None:
+        while f"heads.{i}.0.weight" in sd:
+            h = F.leaky_relu(F.conv2d(feat, sd[f"heads.{i}.0.weight"], sd[f"heads.{i}.0.bias"], 1, 1))
+            outs.append(F.conv2d(h, sd[f"heads.{i}.2.weight"], sd[f"heads.{i}.2.bias"]))
+            i += 1
+    else:
+        hid = []
+        while f"heads.{i}.0.weight" in sd:
+            hid.append(F.leaky_relu(F.conv2d(feat, sd[f"heads.{i}.0.weight"], sd[f"heads.{i}.0.bias"], 1, 1)))
+            i += 1
+        hid = hook(HEADS_HIDDEN_LABEL, torch.cat(hid, 1)).chunk(i, 1)
+        outs = [F.conv2d(h, sd[f"heads.{k}.2.weight"], sd[f"heads.{k}.2.bias"]) for k, h in enumerate(hid)]
+        outs = list(hook(HEADS_OUT_LABEL, torch.cat(outs, 1)).split([o.shape[1] for o in outs], 1))
 
     def nhwc(t):
         return t.permute(0, 2, 3, 1)

@@ -282,6 +282,24 @@ const char* tv_engine_op_kernel(tv_engine* e, int32_t B, int32_t i) {
   return e->e.op_kernel(B, i);
 }
 
+int tv_engine_op_shapes(tv_engine* e, int32_t B, void* stream, int32_t (*shape)[4], int32_t cap, int32_t* n_ops) {
+  TV_GUARD({
+    if (!e || !shape || !n_ops || cap < 0 || B < 1) { set_error("bad argument"); return TV_EINVAL; }
+    int n = 0;
+    int rc = e->e.op_shapes(B, (hipStream_t)stream, shape, cap, &n);
+    *n_ops = n;
+    return rc;
+  })
+}
+
+int tv_engine_op_outputs(tv_engine* e, const void* input, int32_t input_u8, int32_t B, float* out, void* stream,
+                         void* const* dst, int32_t n_dst) {
+  TV_GUARD({
+    if (!e || (n_dst > 0 && !dst) || n_dst < 0) { set_error("bad argument"); return TV_EINVAL; }
+    return e->e.op_outputs(input, input_u8 ? 1 : 0, B, out, (hipStream_t)stream, dst, n_dst);
+  })
+}
+
 int tv_preprocess_u8(const uint8_t* frames, int32_t B, int32_t src_h, int32_t src_w, int32_t dst_h, int32_t dst_w,
                      float* img_nchw, void* stream) {
   TV_GUARD({

@@ -1126,4 +1126,65 @@ int Engine::profile_io(const IoPtrs& io, int input_u8, int B, hipStream_t s, flo
   return rc;
 }
 
+void Engine::op_stored(const Workspace* ws, size_t i, int32_t shape[4]) const {
+  const OpSpec& op = plan.ops[i];
+  shape[0] = shape[1] = shape[2] = shape[3] = 0;
+  switch (ws->route[i].kind) {
+    case Route::StagingInStem:  // never stored: the launch that does this op keeps its result on chip
+    case Route::StemInS2:
+    case Route::DcnInFused:
+    case Route::HeadsFused:
+    case Route::ConvT3Done:     // (the phase-(0,0) op reports the tensor the four phases share)
+    case Route::HeadScatter:    // several of the caller's outputs, none of them an NHWC tensor
+      return;
+    default: break;
+  }
+  if (op.out < 0) {  // the caller's fp32 output buffer
+    const IoSpec& o = plan.outspec(op.out);
+    shape[0] = o.H, shape[1] = o.W, shape[2] = o.cpad, shape[3] = 4;
+    return;
+  }
+  const TensorSpec& t = plan.tensors[op.out];
+  shape[0] = t.H, shape[1] = t.W, shape[2] = t.C, shape[3] = t.f32 ? 4 : (int32_t)dtype_size(dtype);
+}
+
+int Engine::op_shapes(int B, hipStream_t s, int32_t (*shape)[4], int cap, int* n_ops) {
+  TV_HIP(hipSetDevice(device));
+  Workspace* ws = nullptr;
+  int rc = get_workspace(B, s, &ws);
+  if (rc) return rc;
+  const size_t n = plan.ops.size();
+  for (size_t i = 0; i < n && (int)i < cap; ++i) op_stored(ws, i, shape[i]);
+  *n_ops = (int)n;
+  return TV_OK;
+}
+
+int Engine::op_outputs(const void* input, int input_u8, int B, float* out, hipStream_t s, void* const* dst,
+                       int n_dst) {
+  IoPtrs io;
+  int rc = check_io(&input, 1, &out, 1, B, &io);
+  if (rc) return rc;
+  profiled_u8 = input_u8;
+  TV_HIP(hipSetDevice(device));
+  Workspace* ws = nullptr;
+  rc = get_workspace(B, s, &ws);
+  if (rc) return rc;
+  for (size_t k = 0; k < plan.ops.size(); ++k) {
+    const size_t i = (size_t)ws->order[k];
+    rc = run_op(i, ws, io, input_u8, s);
+    if (rc) {
+      set_error("op " + std::to_string(i) + " (" + plan.ops[i].label + "): " + tv_last_error());
+      return rc;
+    }
+    if ((int)i >= n_dst || !dst[i]) continue;
+    int32_t sh[4];
+    op_stored(ws, i, sh);
+    const size_t bytes = (size_t)B * sh[0] * sh[1] * sh[2] * sh[3];
+    const int o = plan.ops[i].out;  // (< 0: the op wrote the caller's output buffer, its data comes from there)
+    const void* from = o < 0 ? (const void*)io.out[-1 - o] : (const char*)ws->arena + ws->off[o];
+    if (bytes && from != dst[i]) TV_HIP(hipMemcpyAsync(dst[i], from, bytes, hipMemcpyDeviceToDevice, s));
+  }
+  return TV_OK;
+}
+
 }  // namespace tv

@@ -201,8 +201,16 @@ struct Engine {
   // or the replay of a graph captured while `insitu` was set)
   int insitu_read(int B, hipStream_t s, float* ms, int cap, int* n_slices);
   const char* op_kernel(int B, size_t i);
+  // diagnostic tap: the stored output of every op of the B-frame workspace on s, shape[i] =
+  // (H, W, C, element bytes) per frame, zeros for an op whose output is never stored (fused into
+  // another launch); the op that writes the caller's output reports that buffer
+  int op_shapes(int B, hipStream_t s, int32_t (*shape)[4], int cap, int* n_ops);
+  // one forward, one op per launch in execution order (as profile()); after op i its stored tensor
+  // is copied to dst[i] (NULL = skip) on s before the next op runs
+  int op_outputs(const void* input, int input_u8, int B, float* out, hipStream_t s, void* const* dst, int n_dst);
 
  private:
+  void op_stored(const Workspace* ws, size_t i, int32_t shape[4]) const;
   const float* weight(const std::string& name, int64_t numel);
   int fold(const std::string& conv, const std::string& bn, int cout, std::vector<double>& scale,
            std::vector<double>& shift);

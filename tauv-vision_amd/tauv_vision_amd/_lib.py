@@ -62,6 +62,8 @@ EXPORTS = {
     "tv_engine_insitu_read": ([c_vp, c_i32, c_vp, ctypes.POINTER(c_f32), c_i32, ctypes.POINTER(c_i32)], c_i32),
     "tv_engine_op_label": ([c_vp, c_i32], ctypes.c_char_p),
     "tv_engine_op_kernel": ([c_vp, c_i32, c_i32], ctypes.c_char_p),
+    "tv_engine_op_shapes": ([c_vp, c_i32, c_vp, ctypes.POINTER(c_i32 * 4), c_i32, ctypes.POINTER(c_i32)], c_i32),
+    "tv_engine_op_outputs": ([c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, ctypes.POINTER(c_vp), c_i32], c_i32),
     "tv_engine_slices": ([c_vp, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)], c_i32),
     "tv_preprocess_u8": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp], c_i32),
     "tv_heatmap_nms": ([c_vp, ctypes.POINTER(c_i64), c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp], c_i32),

@@ -162,6 +162,37 @@ class NativeEngine:
                                                     ctypes.byref(ns)), "insitu_read")
         return [[ms[k * cap + i] for i in range(cap)] for k in range(ns.value)]
 
+    def op_shapes(self, batch, cap=4096):
+        """Per op of the `batch`-frame workspace: (H, W, C, element bytes) of the NHWC tensor it
+        stores, zeros for an op done inside another op's launch (tv_engine_op_shapes)."""
+        sh = ((ctypes.c_int32 * 4) * cap)()
+        n = ctypes.c_int32()
+        _lib.check(_lib.lib().tv_engine_op_shapes(self._h, int(batch), _lib.stream_of(self.device), sh, cap,
+                                                  ctypes.byref(n)), "op_shapes")
+        return [tuple(sh[i]) for i in range(min(n.value, cap))]
+
+    def op_outputs(self, x, out=None):
+        """Diagnostic (per-layer tests): one forward, one op per launch, that keeps every op's stored
+        output: [(label, kernel, tensor-or-None)] per op, the tensor NHWC [B, H, W, C] in the compute
+        dtype (fp32 for fp32 tensors), None for an op that stores nothing of its own. The op that
+        writes the head output gets a copy of `out` (the normal output buffer). `x` is the normalised fp32
+        NCHW input of forward() or uint8 NHWC frames (the forward_u8 path)."""
+        B = x.shape[0]
+        x = x.contiguous()  # (the library reads through the raw pointer)
+        if out is None:
+            out = self.alloc_out(B)
+        shapes = self.op_shapes(B)
+        cdt = {2: torch.float16 if self.desc.compute_dtype == 1 else torch.bfloat16, 4: torch.float32}
+        L = _lib.lib()
+        labels = [L.tv_engine_op_label(self._h, i).decode() for i in range(len(shapes))]
+        bufs = [torch.empty((B, h, w, c), dtype=cdt[eb], device=self.device) if eb else None
+                for (h, w, c, eb) in shapes]
+        dst = (ctypes.c_void_p * len(bufs))(*[None if t is None else t.data_ptr() for t in bufs])
+        _lib.check(L.tv_engine_op_outputs(self._h, ctypes.c_void_p(x.data_ptr()), 1 if x.dtype == torch.uint8 else 0,
+                                          B, ctypes.c_void_p(out.data_ptr()), _lib.stream_of(self.device), dst,
+                                          len(bufs)), "op_outputs")
+        return [(labels[i], L.tv_engine_op_kernel(self._h, B, i).decode(), bufs[i]) for i in range(len(bufs))]
+
     def profile(self, img, out=None, cap=4096):
         """Per-launch (label, ms, flops, kernel) of one forward, timed with HIP events. `img` is the
         normalised fp32 NCHW input of forward() or uint8 NHWC frames (the forward_u8 path)."""
