@@ -83,13 +83,34 @@ typedef enum tv_dtype { TV_F32 = 0, TV_F16 = 1, TV_BF16 = 2, TV_F32X3 = 3 } tv_d
  * reference's permute(0, 2, 3, 1).reshape (prediction_head.py:112-113). Parameters: the reference
  * Yolact state_dict keys without "_backbone.*" ("_feature_pyramid.*", "_masknet.*",
  * "_prediction_head.*"; the Bottleneck blocks in torchvision's layout conv1, bn1, conv2, bn2, conv3,
- * bn3 with bias-free convs); for TV_ARCH_YOLACT_FPN the FeaturePyramid's own keys, unprefixed. */
+ * bn3 with bias-free convs); for TV_ARCH_YOLACT_FPN the FeaturePyramid's own keys, unprefixed.
+ *
+ * TV_ARCH_RESNET18 = the YOLACT backbone (yolact/model/backbone.py:9-32: torchvision's resnet18
+ * tapped at layer2.1.bn2, layer3.1.bn2 and layer4.1.bn2 — the outputs of the last block's second
+ * BatchNorm, before the residual add and the ReLU). Only in_h, in_w and compute_dtype are read.
+ * Input: fp32 NCHW [B, 3, in_h, in_w] (tv_engine_forward_multi with one input). Outputs: the three
+ * taps as fp32 NHWC [B, h, w, 128 / 256 / 512], (h, w) by the conv arithmetic: (in - 1) / 2 + 1 for
+ * the stem, the max-pool and each of layer2..4 (550 -> 275, 138, 69, 35, 18). Parameters:
+ * torchvision's resnet18 keys without "fc.*", unprefixed, in registration order ("conv1.weight",
+ * "bn1.*", "layer1.0.conv1.weight", ..., "layer2.0.downsample.0.weight", "layer2.0.downsample.1.*",
+ * ...; bias-free convs). in_h, in_w >= 1 (a 1 x 1 image gives 1 x 1 taps).
+ *
+ * TV_ARCH_YOLACT = the whole Yolact.forward (model.py:34-60) from the image: TV_ARCH_RESNET18, then
+ * TV_ARCH_YOLACT_HEAD on its taps, which never leave the arena. Input: the image as for
+ * TV_ARCH_RESNET18. Outputs: the four of TV_ARCH_YOLACT_HEAD over the taps' sizes. Head fields as
+ * for TV_ARCH_YOLACT_HEAD (channels[0], downsamples, heights[0..3], n_heads, head_channels,
+ * n_aspect_ratios); the backbone depths are fixed at (128, 256, 512): n_levels, channels[1..],
+ * n_maps, map_h, map_w are ignored. Parameters: the whole reference state_dict, the backbone's keys
+ * under "_backbone._feature_extractor.", then "_feature_pyramid.*", "_masknet.*",
+ * "_prediction_head.*". Several outputs: the single-pointer entry points return TV_EINVAL. */
 #define TV_ARCH_CENTERNET 0
 #define TV_ARCH_DLA34 1
 #define TV_ARCH_PROTONET 2
 #define TV_ARCH_CENTERNET_BACKBONE 3
 #define TV_ARCH_YOLACT_HEAD 4
 #define TV_ARCH_YOLACT_FPN 5
+#define TV_ARCH_RESNET18 6
+#define TV_ARCH_YOLACT 7
 #define TV_MAX_IO 8
 typedef struct tv_model_desc {
   int32_t n_levels;          /* len(backbone_heights) */
@@ -215,6 +236,10 @@ int tv_engine_op_shapes(tv_engine* engine, int32_t batch, void* stream, int32_t 
  * with one input and one output. Asynchronous like tv_engine_forward. */
 int tv_engine_op_outputs(tv_engine* engine, const void* input, int32_t input_u8, int32_t batch, float* out_nhwc,
                          void* stream, void* const* dst, int32_t n_dst);
+/* tv_engine_op_outputs over the buffers of tv_engine_forward_multi (any arch; an op that writes one of
+ * the caller's outputs is read from that buffer; TV_ARCH_YOLACT_HEAD's scatter ops store no tensor). */
+int tv_engine_op_outputs_multi(tv_engine* engine, const float* const* inputs, int32_t n_in, float* const* outputs,
+                               int32_t n_out, int32_t batch, void* stream, void* const* dst, int32_t n_dst);
 /* How a forward of `batch` frames is launched: as *n_slices (1..TV_MAX_SLICES) concurrent slices
  * of slice_batch[0..n_slices) frames, the rest of slice_batch zeroed (diagnostic: per-launch
  * roofline attribution). */
@@ -446,6 +471,16 @@ int tv_diag_convt3(const void* src, int32_t B, int32_t H, int32_t W, int32_t C, 
  * 16-byte vectors, else TV_EINVAL). Async on `stream`; allocates nothing. */
 int tv_diag_bilinear_add(const void* src, int32_t B, int32_t src_h, int32_t src_w, int32_t src_ldc, void* dst,
                          int32_t dst_h, int32_t dst_w, int32_t dst_ldc, int32_t C, int32_t dtype, void* stream);
+
+/* Diagnostics (GPU tests): the ResNet-18 backbone's bandwidth kernels (resnet.hip) on their own.
+ * Compute-dtype NHWC device tensors, C channels in whole 16-byte vectors (else TV_EINVAL). Async on
+ * `stream`; allocate nothing.
+ * tv_diag_maxpool3x3s2: MaxPool2d(3, 2, 1) (floor mode; taps outside the image are ignored):
+ *   src [B, H, W, C] -> out [B, (H - 1) / 2 + 1, (W - 1) / 2 + 1, C].
+ * tv_diag_add_relu: out = relu(a + b), one rounding, over n elements (a multiple of the vector). */
+int tv_diag_maxpool3x3s2(const void* src, int32_t B, int32_t H, int32_t W, int32_t C, void* out, int32_t dtype,
+                         void* stream);
+int tv_diag_add_relu(const void* a, const void* b, void* out, int64_t n, int32_t dtype, void* stream);
 
 const char* tv_last_error(void);
 const char* tv_version(void);

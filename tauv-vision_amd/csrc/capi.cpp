@@ -300,6 +300,15 @@ int tv_engine_op_outputs(tv_engine* e, const void* input, int32_t input_u8, int3
   })
 }
 
+int tv_engine_op_outputs_multi(tv_engine* e, const float* const* inputs, int32_t n_in, float* const* outputs,
+                               int32_t n_out, int32_t B, void* stream, void* const* dst, int32_t n_dst) {
+  TV_GUARD({
+    if (!e || (n_dst > 0 && !dst) || n_dst < 0) { set_error("bad argument"); return TV_EINVAL; }
+    return e->e.op_outputs_multi(reinterpret_cast<const void* const*>(inputs), n_in, outputs, n_out, 0, B,
+                                 (hipStream_t)stream, dst, n_dst);
+  })
+}
+
 int tv_preprocess_u8(const uint8_t* frames, int32_t B, int32_t src_h, int32_t src_w, int32_t dst_h, int32_t dst_w,
                      float* img_nchw, void* stream) {
   TV_GUARD({

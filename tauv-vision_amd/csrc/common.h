@@ -399,6 +399,23 @@ struct HeadScatterParams {
   int nparts, B, HW;
 };
 int launch_head_scatter(const HeadScatterParams& p, hipStream_t s);
+// ResNet-18 backbone bandwidth kernels (resnet.hip): NHWC compute dtype, 16-byte channel vectors.
+// MaxPool2d(3, 2, 1), floor mode, taps outside the image ignored: out [B, (H-1)/2+1, (W-1)/2+1, C]
+int launch_maxpool3x3s2(const void* src, int B, int H, int W, int C, void* out, int dtype, hipStream_t s);
+// out = relu(a + b) over n elements (fp32 sum, one rounding); out overlaps neither input
+int launch_add_relu(const void* a, const void* b, void* out, long long n, int dtype, hipStream_t s);
+// conv1 7x7 / s2 / p3 (3 -> 64, BatchNorm folded) + ReLU + MaxPool2d(3, 2, 1) in one launch, fp16 / bf16:
+// img fp32 NCHW [B, 3, H, W]; w [>= 64][Kpad] compute dtype in the engine's row-expanded stem packing
+// (K = ky * 24 + kx * 3 + c, zero elsewhere); bias fp32 [64]; out NHWC [B, PH, PW, 64], PH = ((H - 1) / 2 + 1 - 1) / 2 + 1
+struct StemPoolParams {
+  const float* img;
+  const void* w;
+  const float* bias;
+  void* out;
+  int B, H, W, Kpad;
+};
+int launch_stem7s2_pool(const StemPoolParams& p, int dtype, int cu_count, hipStream_t s);// n compute-dtype elements -> fp32, exactly
+int launch_store_f32(const void* src, float* out, long long n, int dtype, hipStream_t s);
 // Depth localisation of detections (localize.hip): records [B][K][rec_stride] (y, x, h, w in columns
 // 2-5) or masks [B][n][mh][mw] with det [B][n] rows of box [B][A][4], counts [B], depth
 // [depth_batch][dh][dw] u16 millimetres -> out [B][K or n][8]. Arguments are checked here (return 1

@@ -431,3 +431,20 @@ int diag_conv_small(const void* src, int B, int H, int W, int C, int ldc, const 
 }
 
 }  // namespace tv
+
+// The ResNet-18 backbone's bandwidth kernels on the caller's device tensors (the launchers check
+// the arguments and throw nothing)
+extern "C" int tv_diag_maxpool3x3s2(const void* src, int32_t B, int32_t H, int32_t W, int32_t C, void* out,
+                                    int32_t dtype, void* stream) {
+  const int rc = tv::launch_maxpool3x3s2(src, B, H, W, C, out, dtype, (hipStream_t)stream);
+  return rc == 0 || rc == TV_EHIP ? rc : TV_EINVAL;
+}
+
+extern "C" int tv_diag_add_relu(const void* a, const void* b, void* out, int64_t n, int32_t dtype, void* stream) {
+  if (out == a || out == b) {
+    tv::set_error("add_relu: out overlaps an input");
+    return TV_EINVAL;
+  }
+  const int rc = tv::launch_add_relu(a, b, out, n, dtype, (hipStream_t)stream);
+  return rc == 0 || rc == TV_EHIP ? rc : TV_EINVAL;
+}

@@ -83,7 +83,8 @@ int Engine::pack_op(size_t oi) {
   const int esz = dtype_size(dtype);
   const int BK = 128 / esz;
   if (op.kind == OP_PREP || op.kind == OP_MAXPOOL || op.kind == OP_DCN || op.kind == OP_LAYOUT_IN ||
-      op.kind == OP_BILINEAR_ADD || op.kind == OP_HEAD_SCATTER)
+      op.kind == OP_BILINEAR_ADD || op.kind == OP_HEAD_SCATTER || op.kind == OP_MAXPOOL3S2 || op.kind == OP_ADD_RELU ||
+      op.kind == OP_STORE_F32)
     return TV_OK;
   if (op.kind == OP_DWCONVT_ADD) {  // depthwise ConvTranspose2d weight [C][1][2f][2f] -> fp32 [2f][2f][C]
     const int c = op.N, k = 2 * op.up_s;
@@ -327,6 +328,7 @@ int Engine::create(const tv_model_desc& d, const tv_weight_view* w, int n, int d
     else if (k == "TV_CUS") cu_count = std::max(8, std::min(cu_count, v));
     else if (k == "TV_STEM") stem_mode = v;
     else if (k == "TV_STEMFUSE") stemfuse_mode = v;
+    else if (k == "TV_RSTEM") rstem_mode = v;
     else if (k == "TV_LAT") lat_mode = v;
     else if (k == "TV_LAT_UNITS") lat_units = v;
     else if (k == "TV_LAT_SPLIT") lat_split_max = std::max(1, std::min(8, v));
@@ -393,7 +395,7 @@ int Engine::create(const tv_model_desc& d, const tv_weight_view* w, int n, int d
     for (size_t i = 0; i + 1 < plan.ops.size(); ++i)
       if (plan.ops[i].kind == OP_PREP && plan.ops[i + 1].kind == OP_CONV && plan.ops[i + 1].segs.size() == 1 &&
           plan.ops[i + 1].segs[0].row_expand == 7 && plan.ops[i + 1].N <= 128 && plan.ops[i + 1].N % 8 == 0 &&
-          plan.ops[i + 1].act == 1) {
+          plan.ops[i + 1].act == 1 && plan.ops[i + 1].segs[0].stride == 1) {  // (ResNet's stride-2 stem: the generic GEMMs)
         stem_op = (int)i + 1;
         break;
       }
@@ -431,6 +433,26 @@ int Engine::create(const tv_model_desc& d, const tv_weight_view* w, int n, int d
       ss2_op = stem_op + 1;
     }
   }
+  // ResNet-18's stem (resnet.hip stem7s2_pool): staging, the stride-2 row-expanded 7x7 conv 3 -> 64 with
+  // ReLU and the 3x3 / s2 max-pool of its output, which nothing else reads
+  if (rstem_mode && dtype != F32)
+    for (size_t i = 0; i + 2 < plan.ops.size(); ++i) {
+      const OpSpec& st = plan.ops[i + 1];
+      const OpSpec& mp = plan.ops[i + 2];
+      if (plan.ops[i].kind != OP_PREP || st.kind != OP_CONV || st.segs.size() != 1 || st.segs[0].row_expand != 7 ||
+          st.segs[0].stride != 2 || st.segs[0].src != plan.ops[i].out || st.segs[0].cin != 3 || st.N != 64 ||
+          st.act != 1 || st.out < 0 || mp.kind != OP_MAXPOOL3S2 || mp.src != st.out)
+        continue;
+      bool ok = true;
+      for (size_t j = 0; ok && j < plan.ops.size(); ++j) {
+        if (j == i + 2) continue;
+        const OpSpec& o = plan.ops[j];
+        ok = o.src != st.out && o.add != st.out;
+        for (const SegSpec& sg : o.segs) ok = ok && sg.src != st.out;
+      }
+      if (ok) rstem_op = (int)i + 1;
+      break;
+    }
   packed.resize(plan.ops.size());
   for (size_t i = 0; i < plan.ops.size(); ++i) {
     rc = pack_op(i);
@@ -642,7 +664,18 @@ int Engine::run_op(size_t i, Workspace* ws, const IoPtrs& io, int input_u8, hipS
     case Route::StemInS2:       // the stem runs inside block0.conv1's launch
     case Route::DcnInFused:     // sampled inside the next op's fused DCNv2 kernel
     case Route::ConvT3Done:     // a ConvTranspose2d phase done by the phase-(0,0) op's launch
+    case Route::StemInPool:     // the stem runs inside the max-pool op's launch
       return TV_OK;
+    case Route::StemPool: {
+      const Packed& pk = packed[rstem_op];
+      const StemPoolParams sp{(const float*)io.in[plan.ops[rstem_op - 1].io], pk.w, pk.bias, base + ws->off[op.out],
+                              ws->B, desc.in_h, desc.in_w, pk.Kpad};
+      if (input_u8) {
+        set_error("this model takes the normalised fp32 NCHW image, not u8 frames");
+        return TV_EINVAL;
+      }
+      return launch_stem7s2_pool(sp, dtype, cu_count, s);
+    }
     case Route::Staging: {
       void* dst = base + ws->off[op.out];
       return input_u8 ? launch_prep_u8((const uint8_t*)input, ws->B, desc.in_h, desc.in_w, dst, plan.in_cpad, dtype, s)
@@ -694,6 +727,19 @@ int Engine::run_op(size_t i, Workspace* ws, const IoPtrs& io, int input_u8, hipS
                                      frame, t.C, q.c0, q.n, q.tanh ? 1 : 0};
       }
       return launch_head_scatter(hp, s);
+    }
+    case Route::MaxPool3S2: {
+      const TensorSpec& src = plan.tensors[op.src];
+      return launch_maxpool3x3s2(base + ws->off[op.src], ws->B, src.H, src.W, src.C, base + ws->off[op.out], dtype, s);
+    }
+    case Route::AddRelu: {
+      const TensorSpec& t = plan.tensors[op.out];
+      return launch_add_relu(base + ws->off[op.src], base + ws->off[op.add], base + ws->off[op.out],
+                             (long long)ws->B * t.H * t.W * t.C, dtype, s);
+    }
+    case Route::StoreF32: {
+      const TensorSpec& t = plan.tensors[op.src];
+      return launch_store_f32(base + ws->off[op.src], out, (long long)ws->B * t.H * t.W * t.C, dtype, s);
     }
     case Route::MaxPool:
     case Route::DcnSample:
@@ -1007,6 +1053,11 @@ const char* Engine::op_kernel(int B, size_t i) {
       case Route::BilinearAdd: name = "tv::yh::bilinear_add<" + t + ">"; break;
       case Route::HeadScatter: name = "tv::yh::head_scatter"; break;
       case Route::MaxPool: name = "tv::dla::maxpool2_ceil<" + t + ">"; break;
+      case Route::MaxPool3S2: name = "tv::rn::maxpool3x3s2<" + t + ">"; break;
+      case Route::AddRelu: name = "tv::rn::add_relu<" + t + ">"; break;
+      case Route::StoreF32: name = "tv::rn::store_f32<" + t + ">"; break;
+      case Route::StemPool: name = "tv::rn::stem7s2_pool<" + t + ">"; break;
+      case Route::StemInPool: name = "(fused into the max-pool: stem7s2_pool)"; break;
       case Route::DcnSample: name = "tv::dla::dcn_sample<" + t + ">"; break;
       case Route::DwConvTAdd: name = "tv::dla::dwconvt_add<" + t + ">"; break;
       case Route::ConvT: name = "tv::convt::convt_add<" + t + ", " + str(std::get<ConvTParams>(r.geom).np) + ">"; break;
@@ -1114,6 +1165,7 @@ int Engine::profile_io(const IoPtrs& io, int input_u8, int B, hipStream_t s, flo
       int host = -1;
       const Route kind = ws->route[i].kind;
       if (kind == Route::StemInS2) host = ss2_op;
+      else if (kind == Route::StemInPool) host = (int)i + 1;
       else if (kind == Route::HeadsDone) host = (int)i - 1;
       else if (kind == Route::ConvT3Done) host = (int)i - plan.ops[i].segs[0].convt_phase;
       if (host < 0 || host >= cap) continue;
@@ -1132,6 +1184,7 @@ void Engine::op_stored(const Workspace* ws, size_t i, int32_t shape[4]) const {
   switch (ws->route[i].kind) {
     case Route::StagingInStem:  // never stored: the launch that does this op keeps its result on chip
     case Route::StemInS2:
+    case Route::StemInPool:
     case Route::DcnInFused:
     case Route::HeadsFused:
     case Route::ConvT3Done:     // (the phase-(0,0) op reports the tensor the four phases share)
@@ -1161,8 +1214,13 @@ int Engine::op_shapes(int B, hipStream_t s, int32_t (*shape)[4], int cap, int* n
 
 int Engine::op_outputs(const void* input, int input_u8, int B, float* out, hipStream_t s, void* const* dst,
                        int n_dst) {
+  return op_outputs_multi(&input, 1, &out, 1, input_u8, B, s, dst, n_dst);
+}
+
+int Engine::op_outputs_multi(const void* const* inputs, int n_in, float* const* outputs, int n_out, int input_u8, int B,
+                             hipStream_t s, void* const* dst, int n_dst) {
   IoPtrs io;
-  int rc = check_io(&input, 1, &out, 1, B, &io);
+  int rc = check_io(inputs, n_in, outputs, n_out, B, &io);
   if (rc) return rc;
   profiled_u8 = input_u8;
   TV_HIP(hipSetDevice(device));

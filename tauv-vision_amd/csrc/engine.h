@@ -42,6 +42,8 @@ enum class Route : int {
   Stem, StemS2, StemInS2,      // stem.hip | stem + block0.conv1 in one launch, on conv1's op | the stem op of that pair
   LayoutIn, MaxPool, DcnSample, DwConvTAdd,
   BilinearAdd, HeadScatter,    // yolact_head.hip: the FPN's top-down step | raw head tensors -> the caller's outputs
+  MaxPool3S2, AddRelu, StoreF32,  // resnet.hip: MaxPool2d(3, 2, 1) | relu(a + b) | a tap -> the caller's fp32 output
+  StemPool, StemInPool,        // resnet.hip stem7s2_pool: staging + 7x7 / s2 stem + max-pool in one launch, on the pool's op | the stem op of that pair
   DcnFused, DcnInFused,        // DCNv2 sampling + column GEMM in one kernel, on the GEMM's op | its OP_DCN
   HeadsFused, HeadsDone,       // stacked 3x3 heads with the 1x1 heads in the epilogue | those 1x1 heads' op
   ConvT, ConvT3, ConvT3Done,   // convt.hip | all four phases from the phase-(0,0) op (convt3.hip) | the other three
@@ -157,6 +159,9 @@ struct Engine {
   int stemfuse_mode = 1;       // stem + block0.conv1 (+ the residual's stride-2 stem samples) in one launch
                                // (stem_s2.hip) when the plan has that shape (knob TV_STEMFUSE=0 off)
   int ss2_op = -1;             // op index of block0.conv1 when it runs fused with the stem, else -1
+  int rstem_mode = 1;          // ResNet stem + max-pool in one launch (stem7s2_pool) for fp16/bf16 (knob TV_RSTEM=0: the
+                               // generic row-expanded stem + maxpool3x3s2, which the fp32 paths always take)
+  int rstem_op = -1;           // op index of the stride-2 7x7 stem conv when the plan has that shape (create), else -1
   // concurrent slices: a batch of >= slices * slice_min frames runs as `slices` near-equal parts,
   // the first on the caller's stream and the others on side streams (fork / join events), so one
   // slice's latency-bound small layers and grid tails overlap another's large layers
@@ -208,6 +213,8 @@ struct Engine {
   // one forward, one op per launch in execution order (as profile()); after op i its stored tensor
   // is copied to dst[i] (NULL = skip) on s before the next op runs
   int op_outputs(const void* input, int input_u8, int B, float* out, hipStream_t s, void* const* dst, int n_dst);
+  int op_outputs_multi(const void* const* inputs, int n_in, float* const* outputs, int n_out, int input_u8, int B,
+                       hipStream_t s, void* const* dst, int n_dst);  // every arch
 
  private:
   void op_stored(const Workspace* ws, size_t i, int32_t shape[4]) const;

@@ -339,6 +339,7 @@ static int build_plan_arch(const tv_model_desc& d, Plan* plan) {
   if (d.arch == TV_ARCH_DLA34) return build_plan_dla34(d, plan);
   if (d.arch == TV_ARCH_PROTONET) return build_plan_protonet(d, plan);
   if (d.arch == TV_ARCH_YOLACT_HEAD || d.arch == TV_ARCH_YOLACT_FPN) return build_plan_yolact_head(d, plan);
+  if (d.arch == TV_ARCH_RESNET18 || d.arch == TV_ARCH_YOLACT) return build_plan_resnet(d, plan);
   if (d.arch != TV_ARCH_CENTERNET && d.arch != TV_ARCH_CENTERNET_BACKBONE) {
     set_error("unknown model arch");
     return TV_EINVAL;

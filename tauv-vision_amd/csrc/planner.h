@@ -49,7 +49,11 @@ enum OpKind {
                       // the YOLACT neck's backbone maps)
   // YOLACT neck and head (planner_yolact_head.cpp)
   OP_BILINEAR_ADD = 7, // out += F.interpolate(src, size of out, "bilinear") in place (feature_pyramid.py:49-50)
-  OP_HEAD_SCATTER = 8  // one level's fp32 raw head tensors -> the caller's [A_total, width] outputs (`parts`)
+  OP_HEAD_SCATTER = 8, // one level's fp32 raw head tensors -> the caller's [A_total, width] outputs (`parts`)
+  // ResNet-18 backbone (planner_resnet.cpp): elementwise / window ops on HBM bandwidth (resnet.hip)
+  OP_MAXPOOL3S2 = 9,   // MaxPool2d(3, 2, 1) of `src` (floor mode, taps outside the image ignored)
+  OP_ADD_RELU = 10,    // out = relu(src + add): the residual add after a tapped bn2 (backbone.py:21-23)
+  OP_STORE_F32 = 11    // `src` -> the caller's fp32 NHWC output -1 - out, exactly (a tap that also stays in the arena)
 };
 
 // One part of an OP_HEAD_SCATTER: columns [c0, c0 + n) of the fp32 NHWC tensor `src` ([H, W, ldc],
@@ -125,5 +129,17 @@ int build_plan_protonet(const tv_model_desc& d, Plan* plan);  // planner_protone
 // to a plan, the prototypes going to the caller's output `out_slot`; returns their IoSpec
 IoSpec append_protonet(Plan& P, const std::string& prefix, int x, int F, int k, int out_slot);
 int build_plan_yolact_head(const tv_model_desc& d, Plan* plan);  // planner_yolact_head.cpp
+// The neck and head (TV_ARCH_YOLACT_HEAD; the FeaturePyramid alone for TV_ARCH_YOLACT_FPN) of a
+// checked desc appended to a plan: parameters, ops and the caller's outputs. `maps` empty: the
+// backbone maps are the caller's inputs (one OP_LAYOUT_IN each, sizes from d.map_h / map_w); else
+// the plan's NHWC tensors `maps` (d.n_levels of them, d.channels[1 + i] channels) feed the lateral
+// convs as they are.
+int check_yolact_head_desc(const tv_model_desc& d);
+void append_yolact_head(Plan& P, const tv_model_desc& d, const std::vector<int>& maps);
+// planner_resnet.cpp: torchvision resnet18's parameters (keys prefixed, no fc) and its forward over
+// the staged image tensor `img` (row-expanded for the 7x7 stem, as build_plan's) appended to a
+// plan; returns the three tap tensors (layer2.1.bn2, layer3.1.bn2, layer4.1.bn2)
+std::vector<int> append_resnet18(Plan& P, const std::string& prefix, int img);
+int build_plan_resnet(const tv_model_desc& d, Plan* plan);  // TV_ARCH_RESNET18, TV_ARCH_YOLACT
 
 }  // namespace tv

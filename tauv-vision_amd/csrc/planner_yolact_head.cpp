@@ -35,6 +35,7 @@ struct HeadWalker {
   Plan& P;
   const int F;
   const bool head;
+  const std::vector<int>& given;  // the backbone maps when they are tensors of the plan already (else empty)
 
   void add(const std::string& n, std::vector<int64_t> s) { P.params.push_back({n, std::move(s)}); }
   void conv_p(const std::string& p, int cout, int cin, int k, bool bias = true) {
@@ -98,21 +99,28 @@ struct HeadWalker {
     return sg;
   }
 
+  // backbone map i, one of the caller's inputs, as an NHWC tensor
+  int layout_in(int i) {
+    const int c = d.channels[1 + i];
+    const int x = tensor(d.map_h[i], d.map_w[i], c);
+    P.ins.push_back(IoSpec{d.map_h[i], d.map_w[i], c, c});
+    OpSpec op;
+    op.kind = OP_LAYOUT_IN;
+    op.label = "backbone map " + std::to_string(i) + " NCHW fp32 -> NHWC";
+    op.out = x;
+    op.N = c;
+    op.io = i;
+    P.ops.push_back(op);
+    return x;
+  }
+
   // feature_pyramid.py:44-58 -> the FPN levels' tensors
   std::vector<int> fpn(const std::string& p) {
     const int n = d.n_levels;
     std::vector<int> lat(n);
     for (int i = 0; i < n; ++i) {
       const int c = d.channels[1 + i];
-      const int x = tensor(d.map_h[i], d.map_w[i], c);
-      P.ins.push_back(IoSpec{d.map_h[i], d.map_w[i], c, c});
-      OpSpec op;
-      op.kind = OP_LAYOUT_IN;
-      op.label = "backbone map " + std::to_string(i) + " NCHW fp32 -> NHWC";
-      op.out = x;
-      op.N = c;
-      op.io = i;
-      P.ops.push_back(op);
+      const int x = given.empty() ? layout_in(i) : given[i];
       const std::string w = p + "_lateral_layers." + std::to_string(i);
       lat[i] = conv(w, {seg(x, w, "", c, 1, 1)}, F, 0);
     }
@@ -241,8 +249,8 @@ struct HeadWalker {
 
 }  // namespace
 
-int build_plan_yolact_head(const tv_model_desc& d, Plan* plan) {
-  const bool head = d.arch == TV_ARCH_YOLACT_HEAD;
+int check_yolact_head_desc(const tv_model_desc& d) {
+  const bool head = d.arch != TV_ARCH_YOLACT_FPN;
   if (d.compute_dtype < 0 || d.compute_dtype > 2 || d.n_levels < 1 || d.downsamples < 0 ||
       d.n_levels + d.downsamples > kMaxIO) {
     set_error("yolact head desc: need 1..8 backbone maps and FPN levels in all");
@@ -286,9 +294,19 @@ int build_plan_yolact_head(const tv_model_desc& d, Plan* plan) {
       return TV_ESHAPE;
     }
   }
-  *plan = Plan();
-  HeadWalker w{d, *plan, F, head};
+  return TV_OK;
+}
+
+void append_yolact_head(Plan& P, const tv_model_desc& d, const std::vector<int>& maps) {
+  HeadWalker w{d, P, d.channels[0], d.arch != TV_ARCH_YOLACT_FPN, maps};
   w.run();
+}
+
+int build_plan_yolact_head(const tv_model_desc& d, Plan* plan) {
+  const int rc = check_yolact_head_desc(d);
+  if (rc) return rc;
+  *plan = Plan();
+  append_yolact_head(*plan, d, {});
   for (const ParamInfo& p : plan->params) plan->names.insert(p.name);
   for (auto& op : plan->ops) plan->flops_per_frame += op.flops;
   plan->in_channels = d.channels[1];

@@ -92,15 +92,31 @@ struct Planner {
         case OP_DWCONVT_ADD: kind(i) = Route::DwConvTAdd; break;
         case OP_BILINEAR_ADD: kind(i) = Route::BilinearAdd; break;
         case OP_HEAD_SCATTER: kind(i) = Route::HeadScatter; break;
+        case OP_MAXPOOL3S2: kind(i) = Route::MaxPool3S2; break;
+        case OP_ADD_RELU: kind(i) = Route::AddRelu; break;
+        case OP_STORE_F32: kind(i) = Route::StoreF32; break;
       }
     }
     if (e.stem_op >= 0) kind(e.stem_op) = e.ss2_op >= 0 ? Route::StemInS2 : Route::Stem;
     if (e.ss2_op >= 0) kind(e.ss2_op) = Route::StemS2;
   }
 
+  // 0. stem7s2_pool (the max-pool op from MaxPool3S2, its stem conv from the initial ConvIgemm, their
+  // staging op from Staging): the ResNet stem pair Engine::create found runs staging, conv, ReLU and
+  // pooling as one launch on the pool's op (resnet.hip). Before plan_arena: neither the staged image
+  // nor the conv output then needs arena space.
+  void pass_stem_pool() {
+    if (e.rstem_op < 0) return;
+    const size_t i = (size_t)e.rstem_op;
+    if (kind(i - 1) != Route::Staging || kind(i) != Route::ConvIgemm || kind(i + 1) != Route::MaxPool3S2) return;
+    kind(i - 1) = Route::StagingInStem;
+    kind(i) = Route::StemInPool;
+    kind(i + 1) = Route::StemPool;
+  }
+
   // Liveness-planned arena: a tensor lives from its producing op's level to its last reader's;
   // first-fit placement of each new tensor into the gaps left by dead ones. The outputs of
-  // StagingInStem, StemInS2 and DcnInFused ops are never stored and get no space.
+  // StagingInStem, StemInS2, StemInPool and DcnInFused ops are never stored and get no space.
   void plan_arena() {
     const size_t nt = plan.tensors.size();
     std::vector<int> last(nt, -1);
@@ -139,7 +155,8 @@ struct Planner {
     for (const int i : ws.order) {
       const OpSpec& op = plan.ops[i];
       live.erase(std::remove_if(live.begin(), live.end(), [&](const Live& l) { return l.last < ws.level[i]; }), live.end());
-      if (op.out < 0 || kind(i) == Route::StagingInStem || kind(i) == Route::StemInS2 || kind(i) == Route::DcnInFused)
+      if (op.out < 0 || kind(i) == Route::StagingInStem || kind(i) == Route::StemInS2 || kind(i) == Route::StemInPool ||
+          kind(i) == Route::DcnInFused)
         continue;
       place(op.out);
       if (op.out2 >= 0) place(op.out2);
@@ -652,7 +669,7 @@ struct Planner {
 
   void run() {
     ws.B = B, ws.kname.assign(nops, std::string());
-    plan_levels(); fixed_routes(); plan_arena(); conv_geometry();
+    plan_levels(); fixed_routes(); pass_stem_pool(); plan_arena(); conv_geometry();
     // the kernel choice: each pass may only take an op from the routes its comment names
     pass_generic(); pass_conv3x3(); pass_conv3x3s2(); pass_conv_small(); pass_dcn(); pass_heads();
     pass_convt(); pass_convt3(); pass_conv_lat(); pass_conv_burst(); pass_conv1x1();

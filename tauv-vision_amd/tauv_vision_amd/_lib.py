@@ -64,6 +64,8 @@ EXPORTS = {
     "tv_engine_op_kernel": ([c_vp, c_i32, c_i32], ctypes.c_char_p),
     "tv_engine_op_shapes": ([c_vp, c_i32, c_vp, ctypes.POINTER(c_i32 * 4), c_i32, ctypes.POINTER(c_i32)], c_i32),
     "tv_engine_op_outputs": ([c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, ctypes.POINTER(c_vp), c_i32], c_i32),
+    "tv_engine_op_outputs_multi": ([c_vp, ctypes.POINTER(c_vp), c_i32, ctypes.POINTER(c_vp), c_i32, c_i32, c_vp,
+                                    ctypes.POINTER(c_vp), c_i32], c_i32),
     "tv_engine_slices": ([c_vp, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)], c_i32),
     "tv_preprocess_u8": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp], c_i32),
     "tv_heatmap_nms": ([c_vp, ctypes.POINTER(c_i64), c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp], c_i32),
@@ -102,6 +104,8 @@ EXPORTS = {
     "tv_diag_conv_burst": ([c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32,
                             c_vp], c_i32),
     "tv_diag_burst_plan": ([ctypes.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32)], c_i32),
+    "tv_diag_maxpool3x3s2": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp], c_i32),
+    "tv_diag_add_relu": ([c_vp, c_vp, c_vp, c_i64, c_i32, c_vp], c_i32),
     "tv_last_error": ([], ctypes.c_char_p),
     "tv_version": ([], ctypes.c_char_p),
 }

@@ -193,6 +193,21 @@ class NativeEngine:
                                           len(bufs)), "op_outputs")
         return [(labels[i], L.tv_engine_op_kernel(self._h, B, i).decode(), bufs[i]) for i in range(len(bufs))]
 
+    def op_outputs_multi(self, inputs, outputs):
+        """op_outputs() over the buffers of forward_multi: [(label, kernel, tensor-or-None)] per op."""
+        B = inputs[0].shape[0]
+        shapes = self.op_shapes(B)
+        cdt = {2: torch.float16 if self.desc.compute_dtype == 1 else torch.bfloat16, 4: torch.float32}
+        L = _lib.lib()
+        labels = [L.tv_engine_op_label(self._h, i).decode() for i in range(len(shapes))]
+        bufs = [torch.empty((B, h, w, c), dtype=cdt[eb], device=self.device) if eb else None
+                for (h, w, c, eb) in shapes]
+        dst = (ctypes.c_void_p * len(bufs))(*[None if t is None else t.data_ptr() for t in bufs])
+        _lib.check(L.tv_engine_op_outputs_multi(self._h, self._ptrs(inputs), len(inputs), self._ptrs(outputs),
+                                                len(outputs), B, _lib.stream_of(self.device), dst, len(bufs)),
+                   "op_outputs")
+        return [(labels[i], L.tv_engine_op_kernel(self._h, B, i).decode(), bufs[i]) for i in range(len(bufs))]
+
     def profile(self, img, out=None, cap=4096):
         """Per-launch (label, ms, flops, kernel) of one forward, timed with HIP events. `img` is the
         normalised fp32 NCHW input of forward() or uint8 NHWC frames (the forward_u8 path)."""

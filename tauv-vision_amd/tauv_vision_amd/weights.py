@@ -8,7 +8,9 @@ import torch
 from . import _lib
 
 
-ARCH_CENTERNET, ARCH_DLA34, ARCH_PROTONET, ARCH_CENTERNET_BACKBONE, ARCH_YOLACT_HEAD, ARCH_YOLACT_FPN = range(6)
+(ARCH_CENTERNET, ARCH_DLA34, ARCH_PROTONET, ARCH_CENTERNET_BACKBONE, ARCH_YOLACT_HEAD, ARCH_YOLACT_FPN, ARCH_RESNET18,
+ ARCH_YOLACT) = range(8)
+RESNET18_DEPTHS = (128, 256, 512)  # layer2.1.bn2, layer3.1.bn2, layer4.1.bn2 (yolact/model/backbone.py:21-32)
 
 
 def model_desc(heights, channels, downsamples, head_channels, in_h=64, in_w=64, precision="fp32",
@@ -66,6 +68,24 @@ def yolact_head_desc(in_depths, map_sizes, feature_depth, n_fpn_downsample_layer
     for i, (h, w) in enumerate(map_sizes):
         d.map_h[i], d.map_w[i] = int(h), int(w)
     d.n_aspect_ratios = int(n_aspect_ratios)
+    return d
+
+
+def resnet18_desc(in_h=64, in_w=64, precision="fp32"):
+    """The YOLACT backbone (ARCH_RESNET18: torchvision's resnet18 tapped at layer2.1.bn2, layer3.1.bn2,
+    layer4.1.bn2) over an in_h x in_w image; the structure is fixed."""
+    return model_desc([], [64], 0, [], in_h, in_w, precision, arch=ARCH_RESNET18)
+
+
+def yolact_desc(in_h, in_w, feature_depth, n_fpn_downsample_layers, n_classes, n_prototype_masks, n_aspect_ratios,
+                layers=(0, 0, 0, 0), precision="fp32"):
+    """The whole Yolact.forward from an in_h x in_w image (ARCH_YOLACT): the ResNet-18 backbone, then the
+    head fields of yolact_head_desc over its taps (depths fixed at RESNET18_DEPTHS, sizes by the conv
+    arithmetic). Keys: the whole reference state_dict."""
+    d = yolact_head_desc(RESNET18_DEPTHS, [], feature_depth, n_fpn_downsample_layers, n_classes, n_prototype_masks,
+                         n_aspect_ratios, layers, precision)
+    d.arch = ARCH_YOLACT
+    d.in_h, d.in_w = int(in_h), int(in_w)
     return d
 
 

@@ -19,7 +19,7 @@ import torch.nn as nn
 from . import _lib
 from .dla import populate
 from .engine import NativeEngine
-from .weights import model_io, param_layout, protonet_desc, yolact_head_desc
+from .weights import model_io, param_layout, protonet_desc, resnet18_desc, yolact_desc, yolact_head_desc
 
 
 @dataclass
@@ -522,11 +522,78 @@ class YolactHead(_NativeNet):
         return outs[0], outs[1], outs[2], self.anchor(levels, dev), outs[3][..., :k].permute(0, 3, 1, 2)
 
 
+def _image(img):
+    """The network input as a contiguous fp32 NCHW tensor on its CUDA device; refuses anything else
+    before a launch."""
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise ValueError(f"expected img [batch, 3, in_h, in_w], got {tuple(img.shape)}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
+    if not img.is_cuda:
+        raise ValueError(f"img is on {img.device}; it must be on a CUDA device")
+    return img.to(torch.float32).contiguous()
+
+
+class Resnet101Backbone(_NativeNet):
+    """yolact/model/backbone.py:9-32 (the reference's class name; the network is torchvision's
+    resnet18): img [B, 3, H, W] -> (c3, c4, c5), the outputs of layer2.1.bn2, layer3.1.bn2 and
+    layer4.1.bn2 — each the last block's second BatchNorm, before the residual add and the ReLU —
+    with 128 / 256 / 512 channels at strides 8 / 16 / 32. One native call (TV_ARCH_RESNET18): the
+    7x7 stem, the 3x3 max-pool, the BasicBlocks as GEMMs with BatchNorm folded and the residual as a
+    K-segment. Each result is a [B, C, h, w] view of an fp32 NHWC tensor; `out`: caller-owned NHWC
+    buffers [B, h, w, C].
+
+    The parameters sit in the sub-module `_feature_extractor` under torchvision's names (`conv1`,
+    `bn1`, `layerL.B.conv1|bn1|conv2|bn2`, `layerL.0.downsample.0|1`; no `fc`), so the `_backbone.*`
+    part of a reference Yolact state_dict loads unchanged. torchvision is not a dependency: the
+    names and the forward are restated from its resnet.py."""
+
+    depths = (128, 256, 512)
+
+    def __init__(self, config=None, precision: str = "fp32"):
+        super().__init__()
+        self.config = config
+        self._init_native(precision)
+        layout = [("_feature_extractor." + k, s) for k, s in param_layout(resnet18_desc())]
+        populate(self, layout, seed_layout=layout)
+
+    @staticmethod
+    def map_sizes(in_h, in_w):
+        """(h, w) of c3, c4, c5 for an in_h x in_w image: (x - 1) // 2 + 1 per stride-2 stage."""
+        def half(v):
+            return (int(v) - 1) // 2 + 1
+        h, w = half(half(in_h)), half(half(in_w))
+        out = []
+        for _ in range(3):
+            h, w = half(h), half(w)
+            out.append((h, w))
+        return out
+
+    def backbone_state_dict(self):
+        n = len("_feature_extractor.")
+        return {k[n:]: v for k, v in self.state_dict().items()}
+
+    def forward_nhwc(self, img, out=None):
+        x = _image(img)
+        B, _, H, W = x.shape
+        dev = x.device
+        eng = self._engine((dev.index, (H, W)), lambda: resnet18_desc(H, W, self.precision), self.backbone_state_dict)
+        outs = _outputs(out, [(B, h, w, cp) for h, w, _, cp in model_io(eng.desc)[1]], dev, "Resnet101Backbone")
+        eng.forward_multi([x], outs)
+        return tuple(outs)
+
+    def forward(self, img, out=None):
+        return tuple(o.permute(0, 3, 1, 2) for o in self.forward_nhwc(img, out))
+
+
 class Yolact(YolactHead):
-    """model.py:18-60 with the caller's backbone: `backbone(img)` -> the three maps (any nn.Module,
-    e.g. a torchvision feature extractor under PyTorch-ROCm; `in_depths` defaults to its `depths`
-    attribute, else the reference backbone's (128, 256, 512)), then YolactHead. A reference Yolact
-    state_dict loads as a whole when the backbone has the reference's parameter names."""
+    """model.py:18-60. With `backbone=Resnet101Backbone(config, precision)` the whole forward from the
+    image is one native plan (TV_ARCH_YOLACT): the backbone's taps feed the lateral convs straight
+    from the arena, one engine per (device, image size, precision), and a reference
+    `Yolact.state_dict()` loads as a whole with strict=True. With any other backbone module
+    `backbone(img)` -> the three maps runs first (e.g. a torchvision feature extractor under
+    PyTorch-ROCm; `in_depths` defaults to its `depths` attribute, else the reference backbone's
+    (128, 256, 512)), then YolactHead. Returns YolactHead's five tensors; `out` as YolactHead's."""
 
     def __init__(self, config, backbone: Optional[nn.Module] = None, precision: str = "fp32", in_depths=None):
         if in_depths is None:
@@ -534,10 +601,43 @@ class Yolact(YolactHead):
         super().__init__(in_depths, config, precision)
         if backbone is not None:
             self._backbone = backbone
+        if self._native():
+            if self.in_depths != Resnet101Backbone.depths:
+                raise ValueError(f"in_depths {self.in_depths}: the native backbone gives {Resnet101Backbone.depths}")
+            self.set_precision(precision)
+
+    def _native(self):
+        return isinstance(getattr(self, "_backbone", None), Resnet101Backbone)
+
+    def set_precision(self, precision: str):
+        super().set_precision(precision)
+        if self._native():  # (the backbone's own precision serves a direct call of it; kept equal)
+            self._backbone.precision = precision
+            self._backbone.invalidate()
+
+    def _version_key(self):
+        return super()._version_key() + ((self._backbone._version,) if self._native() else ())
 
     def forward(self, img, out=None):
         if getattr(self, "_backbone", None) is None:
             raise RuntimeError("Yolact was built without a backbone: the ResNet is not part of this library. Pass "
                                "backbone=<nn.Module returning (c3, c4, c5)>, or run your backbone yourself and call "
                                "YolactHead((c3, c4, c5))")
-        return super().forward(self._backbone(img), out)
+        if not self._native():
+            return super().forward(self._backbone(img), out)
+        x = _image(img)
+        B, _, H, W = x.shape
+        levels = self.level_sizes(Resnet101Backbone.map_sizes(H, W))
+        if len(levels) > len(self.config.anchor_scales):
+            raise ValueError(f"{len(levels)} FPN levels but {len(self.config.anchor_scales)} anchor_scales")
+        dev = x.device
+        c = self.config
+        eng = self._engine((dev.index, ("img", H, W)),
+                           lambda: yolact_desc(H, W, int(c.feature_depth), int(c.n_fpn_downsample_layers),
+                                               int(c.n_classes), int(c.n_prototype_masks),
+                                               len(c.anchor_aspect_ratios), _head_layers(c), self.precision),
+                           self.state_dict)
+        (A, _, c1, _), _, (_, _, k, _), (ph, pw, _, kp) = model_io(eng.desc)[1]
+        outs = _outputs(out, [(B, A, c1), (B, A, 4), (B, A, k), (B, ph, pw, kp)], dev, "Yolact")
+        eng.forward_multi([x], outs)
+        return outs[0], outs[1], outs[2], self.anchor(levels, dev), outs[3][..., :k].permute(0, 3, 1, 2)
