@@ -76,8 +76,10 @@ import torch.nn.functional as F
 import oracle
 from oracle.ref_forward import HEADS_HIDDEN_LABEL, HEADS_OUT_LABEL, pad_to_match
 
-U = {"fp16": 2.0 ** -11, "bf16": 2.0 ** -8}
-TORCH_DTYPE = {"fp16": torch.float16, "bf16": torch.bfloat16}
+# ("fp32": the operands are exact, u is the fp32 unit roundoff; used by tests/yolact_layer_ref.py on the
+# routes the fp32 plan takes: its bound is K 2^-24 A + 2^-24 |ref|)
+U = {"fp16": 2.0 ** -11, "bf16": 2.0 ** -8, "fp32": 2.0 ** -24}
+TORCH_DTYPE = {"fp16": torch.float16, "bf16": torch.bfloat16, "fp32": torch.float32}
 # Largest err / (u (|ref| + Q)) of the emulated reference arithmetic over every layer of every GPU
 # case (test_layer_ref_cpu.test_emulation_within_bounds_and_measures_c), and the asserted constant
 C_MEASURED = {"fp16": 1.96, "bf16": 2.31}
