@@ -482,6 +482,22 @@ int tv_diag_maxpool3x3s2(const void* src, int32_t B, int32_t H, int32_t W, int32
                          void* stream);
 int tv_diag_add_relu(const void* a, const void* b, void* out, int64_t n, int32_t dtype, void* stream);
 
+/* Diagnostics (GPU tests): CenterpointDLA34's bandwidth kernels (dla34.hip) on their own. Compute-dtype
+ * NHWC device tensors, C channels in whole 16-byte chunks (else TV_EINVAL, nothing written). Async on
+ * `stream`; allocate nothing.
+ * tv_diag_maxpool2: MaxPool2d(2, 2, ceil_mode=True): src [B, H, W, C] -> out [B, (H + 1) / 2, (W + 1) / 2, C].
+ * tv_diag_dwconvt_add: out = pad_to_match(ConvTranspose2d(C, C, 2f, stride f, padding f / 2, groups = C,
+ *   no bias)(src)) + add (IDAUp.forward, centerpoint_dla.py:453-460). src [B, h, w, C]; weight: device
+ *   fp32 [2f][2f][C] (tap-major, channel-minor); add [B, tH, tW, add_ldc] (add_ldc >= C, whole chunks);
+ *   out [B, tH, tW, C], no alias of src or add. Target pixel (y, x) reads the up-sampled map at
+ *   (y - sy, x - sx), zero outside it; sy, sx >= 0 (else TV_EINVAL). f = 2, 4, 8 on a power-of-two
+ *   chunk count take the shift-and-mask kernel, everything else the generic one. */
+int tv_diag_maxpool2(const void* src, int32_t B, int32_t H, int32_t W, int32_t C, void* out, int32_t dtype,
+                     void* stream);
+int tv_diag_dwconvt_add(const void* src, int32_t B, int32_t h, int32_t w, int32_t C, const float* weight, int32_t f,
+                        const void* add, int32_t add_ldc, void* out, int32_t tH, int32_t tW, int32_t sy, int32_t sx,
+                        int32_t dtype, void* stream);
+
 const char* tv_last_error(void);
 const char* tv_version(void);
 

@@ -440,6 +440,29 @@ extern "C" int tv_diag_maxpool3x3s2(const void* src, int32_t B, int32_t H, int32
   return rc == 0 || rc == TV_EHIP ? rc : TV_EINVAL;
 }
 
+// CenterpointDLA34's bandwidth kernels (dla34.hip) on the caller's device tensors
+extern "C" int tv_diag_maxpool2(const void* src, int32_t B, int32_t H, int32_t W, int32_t C, void* out, int32_t dtype,
+                                void* stream) {
+  if (!src || !out || B < 1 || H < 1 || W < 1) {
+    tv::set_error("maxpool2: null tensor or empty shape");
+    return TV_EINVAL;
+  }
+  const int rc = tv::launch_maxpool2(src, B, H, W, C, out, (H + 1) / 2, (W + 1) / 2, dtype, (hipStream_t)stream);
+  return rc == 0 || rc == TV_EHIP ? rc : TV_EINVAL;
+}
+
+extern "C" int tv_diag_dwconvt_add(const void* src, int32_t B, int32_t h, int32_t w, int32_t C, const float* weight,
+                                   int32_t f, const void* add, int32_t add_ldc, void* out, int32_t tH, int32_t tW,
+                                   int32_t sy, int32_t sx, int32_t dtype, void* stream) {
+  if (!src || !weight || !add || !out || out == add || out == src || B < 1 || h < 1 || w < 1 || tH < 1 || tW < 1) {
+    tv::set_error("dwconvt_add: null or overlapping tensor, or empty shape");
+    return TV_EINVAL;
+  }
+  const int rc = tv::launch_dwconvt_add(src, B, h, w, C, weight, f, add, add_ldc, out, tH, tW, sy, sx, dtype,
+                                        (hipStream_t)stream);
+  return rc == 0 || rc == TV_EHIP ? rc : TV_EINVAL;
+}
+
 extern "C" int tv_diag_add_relu(const void* a, const void* b, void* out, int64_t n, int32_t dtype, void* stream) {
   if (out == a || out == b) {
     tv::set_error("add_relu: out overlaps an input");

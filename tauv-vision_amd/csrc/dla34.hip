@@ -123,7 +123,11 @@ __global__ __launch_bounds__(256) void dcn_sample(const T* __restrict__ x, int B
   }
 }
 
-// weight: fp32 [2f][2f][C] (tap-major, channel-minor). Target pixel (y, x) of the padded and
+// weight: fp32 [2f][2f][C] (tap-major, channel-minor). The at most four products (exact in fp64: a
+// compute-dtype or fp32 value times an fp32 weight) and the skip value are summed in fp64, so that a
+// result the taps and the skip nearly cancel to keeps its relative accuracy (an fp32 sum left it
+// with an error of ~2^-24 of the largest term: the kernel streams memory, the fp64 adds cost nothing);
+// the sum is rounded to fp32 and then to T. Target pixel (y, x) of the padded and
 // cropped map reads the transposed-conv output at (y - sy, x - sx); each output of a k = 2f,
 // s = f transposed conv receives exactly the taps ky = (u + p) mod f (+ f), likewise kx.
 template <typename T>
@@ -144,9 +148,9 @@ __global__ __launch_bounds__(256) void dwconvt_add(const T* __restrict__ src, in
     const unsigned r = pix / (unsigned)tW;
     const int y = (int)(r % (unsigned)tH);
     const unsigned b = r / (unsigned)tH;
-    Vec<T> acc;
+    double acc[V];
 #pragma unroll
-    for (int e = 0; e < V; ++e) acc.v[e] = 0.f;
+    for (int e = 0; e < V; ++e) acc[e] = 0.0;
     const int u = y - sy, v = x - sx;
     if (u >= 0 && u < hu && v >= 0 && v < wu) {
       const int ky0 = (u + p) % f, kx0 = (v + p) % f;
@@ -166,15 +170,15 @@ __global__ __launch_bounds__(256) void dwconvt_add(const T* __restrict__ src, in
           load_vec(src + (((size_t)b * h + iy) * w + ix) * C + q * V, t);
           const float* wp = weight + (ky * k + kx) * C + q * V;
 #pragma unroll
-          for (int e = 0; e < V; ++e) acc.v[e] += t.v[e] * wp[e];
+          for (int e = 0; e < V; ++e) acc[e] += (double)t.v[e] * (double)wp[e];
         }
       }
     }
     Vec<T> s;
     load_vec(add + (size_t)pix * add_ldc + q * V, s);
 #pragma unroll
-    for (int e = 0; e < V; ++e) acc.v[e] = acc.v[e] + s.v[e];
-    store_vec(out + (size_t)pix * C + q * V, acc);
+    for (int e = 0; e < V; ++e) s.v[e] = (float)(acc[e] + (double)s.v[e]);
+    store_vec(out + (size_t)pix * C + q * V, s);
   }
 }
 
@@ -200,9 +204,9 @@ __global__ __launch_bounds__(256) void dwconvt_add_p2(const T* __restrict__ src,
   const unsigned b = r / (unsigned)tH;
   Vec<T> s;
   load_vec(add + (size_t)pix * add_ldc + q * V, s);
-  Vec<T> acc;
+  double acc[V];
 #pragma unroll
-  for (int e = 0; e < V; ++e) acc.v[e] = 0.f;
+  for (int e = 0; e < V; ++e) acc[e] = 0.0;
   const int hu = (h - 1) * f - 2 * p + k, wu = (w - 1) * f - 2 * p + k;
   const int u = y - sy, v = x - sx;
   if (u >= 0 && u < hu && v >= 0 && v < wu) {
@@ -222,13 +226,13 @@ __global__ __launch_bounds__(256) void dwconvt_add_p2(const T* __restrict__ src,
         load_vec(src + (((size_t)b * h + iy) * w + ix) * C + q * V, t);
         const float* wp = weight + (ky * k + kx) * C + q * V;
 #pragma unroll
-        for (int e = 0; e < V; ++e) acc.v[e] += t.v[e] * wp[e];
+        for (int e = 0; e < V; ++e) acc[e] += (double)t.v[e] * (double)wp[e];
       }
     }
   }
 #pragma unroll
-  for (int e = 0; e < V; ++e) acc.v[e] = acc.v[e] + s.v[e];
-  store_vec(out + (size_t)pix * C + q * V, acc);
+  for (int e = 0; e < V; ++e) s.v[e] = (float)(acc[e] + (double)s.v[e]);
+  store_vec(out + (size_t)pix * C + q * V, s);
 }
 
 inline int grid_for(long threads) { return (int)std::max<long>((threads + 255) / 256, 1); }

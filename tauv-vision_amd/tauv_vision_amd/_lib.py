@@ -106,6 +106,9 @@ EXPORTS = {
     "tv_diag_burst_plan": ([ctypes.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32)], c_i32),
     "tv_diag_maxpool3x3s2": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp], c_i32),
     "tv_diag_add_relu": ([c_vp, c_vp, c_vp, c_i64, c_i32, c_vp], c_i32),
+    "tv_diag_maxpool2": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp], c_i32),
+    "tv_diag_dwconvt_add": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,
+                             c_i32, c_i32, c_vp], c_i32),
     "tv_last_error": ([], ctypes.c_char_p),
     "tv_version": ([], ctypes.c_char_p),
 }

@@ -19,7 +19,8 @@ last_level=5, head_conv=256)` and its own `forward` is called unchanged.
 Weights: the seeded recipe of tests/golden/recipe.py over the reference key list (not
 committed; checksums stored). Outputs: .npz inputs/outputs only, no reference source.
 
-Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_golden_dla34.py
+Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_golden_dla34.py [case name ...]
+(with case names: those cases alone; every other .npz and index entry is left as it is)
 """
 import json
 import os
@@ -67,9 +68,18 @@ def _import_dla34():
 
 def main():
     rcfg, rnet, rdec, rdla34 = _import_dla34()
+    only = set(sys.argv[1:])  # case names: regenerate these alone, the other files and index entries stay
+    unknown = only - {c["name"] for c in DLA34_CASES}
+    assert not unknown, f"no such DLA34 case: {sorted(unknown)}"
     index = {}
+    index_path = os.path.join(HERE, "models_dla34.json")
+    if only and os.path.exists(index_path):
+        with open(index_path) as f:
+            index = json.load(f)
     for case in DLA34_CASES:
         name = case["name"]
+        if only and name not in only:
+            continue
         torch.manual_seed(0)
         oc = object_config_for(rcfg, case["objects"])
         head_channels = rnet.get_head_channels(oc)
@@ -113,8 +123,8 @@ def main():
         np.savez_compressed(os.path.join(HERE, f"dla34_{name}.npz"), **out)
         index[name] = {"keys": keys, "head_channels": head_channels, "fields": present, "case": case}
         print(f"{name}: {len(keys)} keys, heads {head_channels}, heatmap {tuple(pred.heatmap.shape)}")
-    with open(os.path.join(HERE, "models_dla34.json"), "w") as f:
-        json.dump(index, f, indent=1)
+    with open(index_path, "w") as f:
+        json.dump({c["name"]: index[c["name"]] for c in DLA34_CASES if c["name"] in index}, f, indent=1)
 
 
 if __name__ == "__main__":

@@ -53,6 +53,11 @@ DLA34_CASES = [
     # 360x640, 4 labels x 1 keypoint; ida_up's pad_to_match shifts one row (92 -> 90, a14)
     dict(name="b1_360x640_kp", in_h=360, in_w=640, batch=1, seed=203,
          objects={"n_labels": 4, "keypoints_per_label": 1}),
+    # odd map widths (every other width is a multiple of 32): 100x104 -> maps 50x52, 25x26, 13x13,
+    # 7x7, 4x4: ceil-mode pooling with an over-hanging last column (13 -> 7, 7 -> 4), pad_to_match
+    # crops in W (14 -> 13, 26 -> 25 rows) and, on ida_up's f = 4 step (7x7 -> 28x28 onto 25x26),
+    # the one-pixel shift on both axes (sy = sx = 1); plain heads
+    dict(name="b1_100x104", in_h=100, in_w=104, batch=1, seed=204, objects=PLAIN4),
 ]
 
 # YOLACT Masknet protonet (masknet.py:8-55): feature_depth F, n_prototype_masks k, fpn[0] size.
