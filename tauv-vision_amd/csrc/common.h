@@ -9,6 +9,7 @@
 #error "tauv_vision_amd kernels are written for gfx950 (MI355X) only"
 #endif
 #include <cstdint>
+#include <cstring>
 #include <string>
 
 namespace tv {
@@ -16,6 +17,15 @@ namespace tv {
 enum DType : int { F32 = 0, F16 = 1, BF16 = 2 };
 
 inline int dtype_size(int dt) { return dt == F32 ? 4 : 2; }
+
+// host: fp32 -> bf16 bits, round to nearest even; a NaN stays a (quiet) NaN
+inline uint16_t f32_to_bf16(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x7FFFFFu)) return (uint16_t)((u >> 16) | 0x40);  // NaN
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
 
 // Thread-local error string behind tv_last_error().
 void set_error(const std::string& msg);

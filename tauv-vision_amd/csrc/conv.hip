@@ -80,8 +80,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_igemm(const ConvParams* __re
   // weight panel) run on the same XCD's L2.
   const int nb = p.mtiles * p.ntiles;
   const int bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-  const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int lin = xcd_linear(bid, nb);
   const int ntile = lin % p.ntiles;
   const int mtile = lin / p.ntiles;
   const int m0 = mtile * kTileM;

@@ -30,12 +30,6 @@ constexpr int KC = 64;                 // channels per chunk (4 MFMA k-steps of 
 constexpr int MAXK = 576;              // K bound: 128 rows x (576 x 2 + 16) B = 149 KiB of weights
 constexpr int LDS_MAX = 160 * 1024;
 
-template <typename T>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  typedef T t2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, t2{(T)a, (T)b});
-}
-
 struct Chunk {
   uint4 x[4];  // B operand: 4 k-steps of 16 channels, lane half lh holding channels 8 lh .. + 8
 };

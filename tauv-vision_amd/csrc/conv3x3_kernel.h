@@ -181,50 +181,6 @@ static_assert(Geo<8, 32>::OFF_W == OFF_W && Geo<8, 16>::HPIX == HPIX && Geo<8, 3
 static_assert(Geo<4, 32>::lds<0, 0>() <= 80 * 1024 && Geo<4, 16>::lds<0, 0>() <= 80 * 1024, "two 4-wave workgroups per CU");
 
 
-typedef __attribute__((address_space(3))) char lds_char;
-typedef const __attribute__((address_space(1))) void gvoid;
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-__device__ void raw_buffer_store_v4(u32x4 data, i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v4i32");
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ u32x2 raw_buffer_load_v2(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v2i32");
-__device__ u32x4 raw_buffer_load_v4(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4i32");
-__device__ void raw_buffer_load_lds(i32x4 rsrc, __attribute__((address_space(3))) void* lds, int size, int voffset,
-                                    int soffset, int offset, int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
-
-__device__ __forceinline__ void dma16(const void* src, lds_char* dst) {
-  __builtin_amdgcn_global_load_lds((gvoid*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
-template <int OFF>
-__device__ __forceinline__ u32x4 ds_read16(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-__device__ __forceinline__ uint4 to_u4(u32x4 v) { return make_uint4(v.x, v.y, v.z, v.w); }
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// s_waitcnt takes an immediate: dispatch the (wave-uniform, exact) count
-__device__ __forceinline__ void wait_vm_n(int n) {
-  switch (n) {
-    case 0: wait_vm<0>(); break;
-    case 1: wait_vm<1>(); break;
-    case 2: wait_vm<2>(); break;
-    case 3: wait_vm<3>(); break;
-    case 4: wait_vm<4>(); break;
-    case 5: wait_vm<5>(); break;
-    case 6: wait_vm<6>(); break;
-    case 7: wait_vm<7>(); break;
-    default: wait_vm<8>(); break;
-  }
-}
-
-template <int V>
-using IC = std::integral_constant<int, V>;
-
 template <int NI>
 struct Half {  // fragments of one 16-deep sub-step
   u32x4 x[2];    // pixel fragments f
@@ -235,11 +191,6 @@ struct Half {  // fragments of one 16-deep sub-step
 // lanes 0-31 hold channels 8k+0..3 (group k) / 8k+8..11 (group k+1) of pixel l, lanes 32-63
 // the +4 halves; one v_permlane32_swap per dword pair gives every lane 8 consecutive channels
 // (lanes 0-31: group k, lanes 32-63: group k+1 of pixel l-32), stored at +8*lh channels.
-template <typename T>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  typedef T t2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, t2{(T)a, (T)b});
-}
 template <typename T>
 __device__ __forceinline__ void store_out(T* dst, const float (&v)[2][4], int lh) {
   const unsigned a0 = pack2<T>(v[0][0], v[0][1]), a1 = pack2<T>(v[0][2], v[0][3]);
@@ -308,17 +259,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
   // epilogue stores are dropped).
   constexpr int UP = NCB == 2 ? 2 : 1;  // units per scheduled item
   const int nitems = (ntot + UP - 1) / UP;
-  const int G = gridDim.x, bid = blockIdx.x;
-  int first, stride, end;
-  if ((G & 7) == 0) {
-    first = (int)((long long)nitems * (bid & 7) / 8) + (bid >> 3);
-    end = (int)((long long)nitems * ((bid & 7) + 1) / 8);
-    stride = G >> 3;
-  } else {
-    first = bid;
-    end = nitems;
-    stride = G;
-  }
+  const XcdRange xr = xcd_range(nitems);
+  const int first = xr.first, end = xr.end, stride = xr.stride;
   const int ntl = first < end ? UP * ((end - first + stride - 1) / stride) : 0;
   if (ntl == 0) return;
 #if TV_C3_EXP == 9
@@ -336,24 +278,19 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
   for (int c = tid; c < ntiles * BN; c += NT) lbias[c] = c < p.N ? p.bias[c] : 0.0f;
 
   // ---- sources
-  i32x4 rsrc;
-  {
-    const unsigned long long a = (unsigned long long)sg.src;
-    rsrc.x = (int)(unsigned)a;
-    rsrc.y = (int)(unsigned)(a >> 32);
-    rsrc.z = (int)(unsigned)((unsigned long long)p.M * ldc * sizeof(T));  // bytes (host checks < 2^31)
-    rsrc.w = 0x00020000;
-  }
+  const i32x4 rsrc = rsrc_of(sg.src, (unsigned)((unsigned long long)p.M * ldc * sizeof(T)));  // bytes (host checks < 2^31)
   // k-step-major weights: [ntile][k-step][BNK rows][64 B], chunks pre-swizzled; one WSL/8 piece
   // per wave per k-step at (ntile * SPT + q) * WSL + wave * WSL / 8
   // (read through a buffer resource: one lane-offset VGPR, the k-step offset in an SGPR)
+  // (wrsrc and the plain epilogue's orsrc are built in place: through rsrc_of() the instruction
+  // order the compiler starts from differs, and with it these kernels' register allocation)
   i32x4 wrsrc;
   {
     const unsigned long long a = (unsigned long long)p.weight;
     wrsrc.x = (int)(unsigned)a;
     wrsrc.y = (int)(unsigned)(a >> 32);
     wrsrc.z = ntiles * SPTK * WSL;
-    wrsrc.w = 0x00020000;
+    wrsrc.w = kRsrcWord3;
   }
   const int wvoff = wave * (WSL / NW) + lane * WPL;
 
@@ -389,7 +326,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
       const int x = x0 - 1 + (int)((gq >> 8) & 0xff);
       const bool ok = gq != ~0u && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
       hoff[i] = ok ? ((unsigned)(ybase + y) * (unsigned)W + (unsigned)x) * pix_bytes + (gq & 0xff) * 16u
-                   : 0x80000000u;
+                   : (unsigned)OOB;
     }
   };
   // one halo piece (index I of this wave's HPW) of channel block cb into buffer bsel
@@ -425,12 +362,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
   }
   auto res_piece = [&](int i, int fr, int y0, int x0, int cb) __attribute__((always_inline)) {
     const unsigned long long fb = (unsigned long long)sr.H * sr.W * rpix_bytes;
-    const unsigned long long a = (unsigned long long)sr.src + (unsigned long long)fr * fb;
-    i32x4 rs;
-    rs.x = (int)(unsigned)a;
-    rs.y = (int)(unsigned)(a >> 32);
-    rs.z = (int)(unsigned)fb;
-    rs.w = 0x00020000;
+    const i32x4 rs = rsrc_of((const void*)((unsigned long long)sr.src + (unsigned long long)fr * fb), (unsigned)fb);
     const int q = (int)(rgeo[i] >> 2), c = (int)(rgeo[i] & 3);
     const int y = y0 + q / TW, x = x0 + q % TW;
     // a phantom unit's frame is past the tensor, and a residual input narrower than the 3x3 input
@@ -438,7 +370,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
     const bool ok = y < H && x < W && fr < nframes && cb * CBK < sr.C;
     const unsigned off = ok ? ((unsigned)(y * sr.stride) * (unsigned)sr.W + (unsigned)(x * sr.stride)) * rpix_bytes +
                                   (unsigned)c * 16u
-                            : 0x80000000u;
+                            : (unsigned)OOB;
     raw_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(lds + OFF_R + (wave * RPW + i) * 1024), 16,
                         (int)off, cb * CBK * (int)sizeof(T), 0, 0);
   };
@@ -513,12 +445,12 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
   auto read_one = [&](auto r, auto j, auto tap, unsigned xb, unsigned wb, Half<NI>& F) __attribute__((always_inline)) {
     constexpr int R = decltype(r)::value, J = decltype(j)::value, TAP = decltype(tap)::value;
     if constexpr (TAP == 9) {
-      if constexpr (R < 2) F.x[R] = ds_read16<R * 2048>(rxa[J]);
-      else F.w[R - 2] = ds_read16<(R - 2) * 2048>(wb);
+      if constexpr (R < 2) F.x[R] = ds_read16_off<R * 2048>(rxa[J]);
+      else F.w[R - 2] = ds_read16_off<(R - 2) * 2048>(wb);
     } else {
       constexpr int TOFF = ((TAP / 3) * RS + (TAP % 3)) * PITCH;
-      if constexpr (R < 2) F.x[R] = ds_read16<TOFF + 32 * J + R * FOFF>(xb);
-      else F.w[R - 2] = ds_read16<(R - 2) * 2048>(wb);
+      if constexpr (R < 2) F.x[R] = ds_read16_off<TOFF + 32 * J + R * FOFF>(xb);
+      else F.w[R - 2] = ds_read16_off<(R - 2) * 2048>(wb);
     }
   };
 
@@ -530,8 +462,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
   // K16: fragment reads (tap 9 = the residual k-step) and the 4 MFMAs of channel fragment I
   [[maybe_unused]] auto rd_x16 = [&](auto f, auto tap, unsigned xb) __attribute__((always_inline)) {
     constexpr int F = decltype(f)::value, TAP = decltype(tap)::value;
-    if constexpr (TAP == 9) return ds_read16<F * 1024>(rxa16);
-    else return ds_read16<((TAP / 3) * RS + (TAP % 3)) * PITCH + FO16[F]>(xb);
+    if constexpr (TAP == 9) return ds_read16_off<F * 1024>(rxa16);
+    else return ds_read16_off<((TAP / 3) * RS + (TAP % 3)) * PITCH + FO16[F]>(xb);
   };
   [[maybe_unused]] auto quad16 = [&](auto i, auto first, const u32x4& w, const u32x4 (&x)[4]) __attribute__((always_inline)) {
     constexpr int I = decltype(i)::value;
@@ -594,9 +526,9 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
         orsrc.x = (int)(unsigned)a;
         orsrc.y = (int)(unsigned)(a >> 32);
         orsrc.z = (int)out_frame_bytes;
-        orsrc.w = 0x00020000;
+        orsrc.w = kRsrcWord3;
         obase = ok ? ((unsigned)(y * W + x) * (unsigned)p.out_ldc + (unsigned)(p.out_coff + n0 + 8 * lh)) * (unsigned)sizeof(OutT)
-                   : 0x80000000u;
+                   : (unsigned)OOB;
       }
       [[maybe_unused]] f32x16 hacc = f32x16{};  // EPI 1: the 1x1 heads' partial sums of this pixel
 #pragma unroll
@@ -626,7 +558,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
             orsrc.z = 0;
 #endif
             raw_buffer_store_v4(u32x4{r0[0], r1[0], r0[1], r1[1]}, orsrc,
-                                ch < p.N ? (int)(obase + (unsigned)((32 * i + 16 * m) * sizeof(OutT))) : (int)0x80000000u, 0, 0);
+                                ch < p.N ? (int)(obase + (unsigned)((32 * i + 16 * m) * sizeof(OutT))) : OOB, 0, 0);
           } else {
             // the 8 hidden channels 32i+16m+8lh.. of this pixel are the MFMA B operand of k-step
             // 2i+m of the 1x1, as a hi + lo pair of T values (hi = T(v), lo = T(v - hi)): the
@@ -716,14 +648,9 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
       const int q = WP * wave + 16 * f + pin;
       const int y = y0 + q / TW, x = x0 + q % TW;
       const bool ok = y < H && x < W && fr < nframes;
-      i32x4 orsrc;
-      const unsigned long long a = (unsigned long long)out_ptr + (unsigned long long)fr * out_frame_bytes;
-      orsrc.x = (int)(unsigned)a;
-      orsrc.y = (int)(unsigned)(a >> 32);
-      orsrc.z = (int)out_frame_bytes;
-      orsrc.w = 0x00020000;
+      const i32x4 orsrc = rsrc_of((const void*)((unsigned long long)out_ptr + (unsigned long long)fr * out_frame_bytes), (unsigned)out_frame_bytes);
       const unsigned obase = ok ? ((unsigned)(y * W + x) * (unsigned)p.out_ldc + (unsigned)(p.out_coff + n0 + cofs16)) * (unsigned)sizeof(OutT)
-                                : 0x80000000u;
+                                : (unsigned)OOB;
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
         float v[2][4];
@@ -744,7 +671,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
         const auto r1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
         const u32x4 hv = u32x4{r0[0], r1[0], r0[1], r1[1]};
         const int ch = n0 + 32 * j + cofs16;
-        raw_buffer_store_v4(hv, orsrc, ch < p.N ? (int)(obase + (unsigned)(32 * j * sizeof(OutT))) : (int)0x80000000u, 0, 0);
+        raw_buffer_store_v4(hv, orsrc, ch < p.N ? (int)(obase + (unsigned)(32 * j * sizeof(OutT))) : OOB, 0, 0);
         __builtin_amdgcn_sched_barrier(0);  // bound the live set: one channel-fragment pair at a time
       }
     }
@@ -781,11 +708,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
     // into the tile loop carry the same VMEM sequence and the compiler's vmcnt for the first
     // weight ds_writes of a tile leaves the previous tile's stores in flight
     __builtin_amdgcn_sched_barrier(0);
-    i32x4 nul;
-    nul.x = (int)(unsigned)(unsigned long long)out_ptr;
-    nul.y = (int)(unsigned)((unsigned long long)out_ptr >> 32);
-    nul.z = 0;
-    nul.w = 0x00020000;
+    const i32x4 nul = rsrc_of(out_ptr, 0);
 #pragma unroll
     for (int k = 0; k < 4 * NI; ++k) raw_buffer_store_v4(u32x4{0u, 0u, 0u, 0u}, nul, k * 16, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
@@ -803,7 +726,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
     X16[0][2] = rd_x16(IC<2>{}, IC<0>{}, xa16);
     X16[0][3] = rd_x16(IC<3>{}, IC<0>{}, xa16);
 #pragma unroll
-    for (int i = 0; i < NI; ++i) W16[0][i] = ds_read16<0>(wa16 + i * 1024);
+    for (int i = 0; i < NI; ++i) W16[0][i] = ds_read16_off<0>(wa16 + i * 1024);
   } else {
     read_one(IC<0>{}, IC<0>{}, IC<0>{}, xa, wa[0], H0);
     read_one(IC<1>{}, IC<0>{}, IC<0>{}, xa, wa[0], H0);
@@ -887,13 +810,13 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
       u32x4(&WA)[NI] = W16[0];
       u32x4(&WB)[NI] = W16[1];
       quad16(IC<0>{}, IC<FIRST>{}, WA[0], X);
-      WB[0] = ds_read16<NI * 1024>(w16c);
-      WB[1] = ds_read16<(NI + 1) * 1024>(w16c);
+      WB[0] = ds_read16_off<NI * 1024>(w16c);
+      WB[1] = ds_read16_off<(NI + 1) * 1024>(w16c);
       __builtin_amdgcn_sched_barrier(0);
       quad16(IC<1>{}, IC<FIRST>{}, WA[1], X);
       if constexpr (NI == 4) {
-        WB[2] = ds_read16<6 * 1024>(w16c);
-        WB[3] = ds_read16<7 * 1024>(w16c);
+        WB[2] = ds_read16_off<6 * 1024>(w16c);
+        WB[3] = ds_read16_off<7 * 1024>(w16c);
       }
 #if TV_C3_EXP != 6
       *reinterpret_cast<WReg*>(smem + OFF_W + ((s + WD) % RG) * WSLOT + wvoff) = wreg[(PAR + WD) & 3];
@@ -926,14 +849,14 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64 * NWV, 64 * NWV), amdgp
       };
       group(IC<0>{});
       w_load(wreg[(PAR + 1) & 3]);
-      WA[0] = ds_read16<0>(w16n);
-      WA[1] = ds_read16<1024>(w16n);
+      WA[0] = ds_read16_off<0>(w16n);
+      WA[1] = ds_read16_off<1024>(w16n);
       X[0] = rd_x16(IC<0>{}, IC<NTAP>{}, x16n);
       __builtin_amdgcn_sched_barrier(0);
       group(IC<1>{});
       if constexpr (NI == 4) {
-        WA[2] = ds_read16<2048>(w16n);
-        WA[3] = ds_read16<3072>(w16n);
+        WA[2] = ds_read16_off<2048>(w16n);
+        WA[3] = ds_read16_off<3072>(w16n);
       }
       X[1] = rd_x16(IC<1>{}, IC<NTAP>{}, x16n);
       __builtin_amdgcn_sched_barrier(0);

@@ -119,66 +119,10 @@ constexpr Sched make_sched() {
 constexpr Sched SCH = make_sched();
 static_assert(SCH.blk[SPT - 1] == 2 * NBLK - 1 && SCH.j[SPT - 1] == PB_J0[BLK_PB[NBLK - 1]] + 1, "schedule covers the tile");
 
-typedef __attribute__((address_space(3))) char lds_char;
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-__device__ u32x4 raw_buffer_load_v4(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4i32");
-__device__ void raw_buffer_load_lds(i32x4 rsrc, __attribute__((address_space(3))) void* lds, int size, int voffset,
-                                    int soffset, int offset, int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
-
-template <int OFF>
-__device__ __forceinline__ u32x4 ds_read16(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-__device__ __forceinline__ uint4 to_u4(u32x4 v) { return make_uint4(v.x, v.y, v.z, v.w); }
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// s_waitcnt takes an immediate: dispatch the (wave-uniform, exact) count
-__device__ __forceinline__ void wait_vm_n(int n) {
-  switch (n) {
-    case 0: wait_vm<0>(); break;
-    case 1: wait_vm<1>(); break;
-    case 2: wait_vm<2>(); break;
-    case 3: wait_vm<3>(); break;
-    case 4: wait_vm<4>(); break;
-    case 5: wait_vm<5>(); break;
-    case 6: wait_vm<6>(); break;
-    case 7: wait_vm<7>(); break;
-    case 8: wait_vm<8>(); break;
-    case 9: wait_vm<9>(); break;
-    case 10: wait_vm<10>(); break;
-    case 11: wait_vm<11>(); break;
-    case 12: wait_vm<12>(); break;
-    default: wait_vm<13>(); break;
-  }
-}
-
-template <int V>
-using IC = std::integral_constant<int, V>;
-
-template <int Q, int N, typename F>
-__device__ __forceinline__ void unroll(F& f) {
-  if constexpr (Q < N) {
-    f(IC<Q>{});
-    unroll<Q + 1, N>(f);
-  }
-}
-
 struct Half {  // fragments of one 16-deep sub-step
   u32x4 x[2];  // pixel fragments f
   u32x4 w[4];  // channel fragments i
 };
-
-template <typename T>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  typedef T t2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, t2{(T)a, (T)b});
-}
 
 template <typename T, int ACT>
 __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_eu(2, 2))) void conv3x3s2(
@@ -202,17 +146,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   const int ntot = p.mtiles;                   // one 128-channel tile (N == 128)
 
   // ---- this block's tiles: XCD-aware contiguous ranges
-  const int G = gridDim.x, bid = blockIdx.x;
-  int first, stride, end;
-  if ((G & 7) == 0) {
-    first = (int)((long long)ntot * (bid & 7) / 8) + (bid >> 3);
-    end = (int)((long long)ntot * ((bid & 7) + 1) / 8);
-    stride = G >> 3;
-  } else {
-    first = bid;
-    end = ntot;
-    stride = G;
-  }
+  const XcdRange xr = xcd_range(ntot);
+  const int first = xr.first, end = xr.end, stride = xr.stride;
   const int ntl = first < end ? (end - first + stride - 1) / stride : 0;
   if (ntl == 0) return;
   const int S_tot = ntl * SPT;
@@ -223,15 +158,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   // ---- sources: one buffer resource per frame (offsets within a frame stay below 2^31)
   const unsigned pix_bytes = (unsigned)ldc * (unsigned)sizeof(T);
   const unsigned long long frame_bytes = (unsigned long long)H * W * pix_bytes;
-  auto rsrc_of = [&](int fr) __attribute__((always_inline)) {
-    i32x4 r;
-    const unsigned long long a = (unsigned long long)sg.src + (unsigned long long)fr * frame_bytes;
-    r.x = (int)(unsigned)a;
-    r.y = (int)(unsigned)(a >> 32);
-    r.z = (int)(unsigned)frame_bytes;
-    r.w = 0x00020000;
-    return r;
-  };
 
   auto tile_of = [&](int idx, int& fr, int& y0, int& x0) __attribute__((always_inline)) {
     const int t = first + idx * stride;
@@ -255,7 +181,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   auto issue_block = [&](int fr, int y0, int x0, int cb, int pb, int buf, auto loc, auto hic) __attribute__((always_inline)) {
     constexpr int LO = decltype(loc)::value, HI = decltype(hic)::value;
     const int pr = pb < 2 ? 1 : 0, pc = (pb & 1) == 0 ? 1 : 0;  // PB_P, PB_Q
-    const i32x4 rs = rsrc_of(fr);
+    const i32x4 rs = rsrc_of((const void*)((unsigned long long)sg.src + (unsigned long long)fr * frame_bytes), (unsigned)frame_bytes);
     lds_char* base = lds + buf * HBUF + pbase * 1024;
     // every wave issues HPW pieces: unconditional VMEM keeps the compiler's vmcnt for the weight
     // ds_write exact (a conditional load makes it vmcnt(0)); waves 4-7 send their 6th, all-OOB
@@ -267,7 +193,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
       const int y = 2 * y0 - pr + 2 * hy, x = 2 * x0 - pc + 2 * hx;
       const bool ok = gq != ~0u && hy < TH + pr && hx < TW + pc && (unsigned)y < (unsigned)H &&
                       (unsigned)x < (unsigned)W;
-      const unsigned off = ok ? ((unsigned)y * (unsigned)W + (unsigned)x) * pix_bytes + (gq & 0xff) * 16u : 0x80000000u;
+      const unsigned off = ok ? ((unsigned)y * (unsigned)W + (unsigned)x) * pix_bytes + (gq & 0xff) * 16u : (unsigned)OOB;
       lds_char* dst = i < npw ? base + i * 1024 : lds + OFF_D;
       raw_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)dst, 16, (int)off, cb * CBK * (int)sizeof(T), 0, 0);
     }
@@ -277,14 +203,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   // through a buffer resource: one lane-offset VGPR, the k-step offset in an SGPR
   int wc_in = 0;
   u32x4 wreg[4];  // k-step q is loaded at step q-5 into set q % 4, written to LDS at step q-2
-  i32x4 wrsrc;
-  {
-    const unsigned long long a = (unsigned long long)p.weight;
-    wrsrc.x = (int)(unsigned)a;
-    wrsrc.y = (int)(unsigned)(a >> 32);
-    wrsrc.z = SPT * WSLOT;
-    wrsrc.w = 0x00020000;
-  }
+  const i32x4 wrsrc = rsrc_of(p.weight, (unsigned)(SPT * WSLOT));
   const int wvoff = wave * 1024 + lane * 16;
   auto w_load = [&](u32x4& dst) __attribute__((always_inline)) {
     dst = raw_buffer_load_v4(wrsrc, wvoff, wc_in * WSLOT, 0);
@@ -304,8 +223,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   auto read_one = [&](auto r, auto sj, auto kj, unsigned xb, unsigned wb, Half& F) __attribute__((always_inline)) {
     constexpr int R = decltype(r)::value, SJ = decltype(sj)::value, KJ = decltype(kj)::value;
     constexpr int TOFF = (J_TY[KJ] * RS + J_TX[KJ]) * PITCH;
-    if constexpr (R < 2) F.x[R] = ds_read16<TOFF + 32 * SJ + R * FOFF>(xb);
-    else F.w[R - 2] = ds_read16<(R - 2) * 2048>(wb);
+    if constexpr (R < 2) F.x[R] = ds_read16_off<TOFF + 32 * SJ + R * FOFF>(xb);
+    else F.w[R - 2] = ds_read16_off<(R - 2) * 2048>(wb);
   };
 
   f32x16 acc[2][4];

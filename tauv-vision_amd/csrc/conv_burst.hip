@@ -37,33 +37,6 @@ constexpr int SR = 36;                  // partial-tile row pitch (floats)
 constexpr int PART = PX * SR * 4;       // one wave's partial tile
 constexpr int ZERO_BYTES = 256;         // LDS zeros: A operand of the padding k-steps
 constexpr int LDS_MAX = 160 * 1024;
-constexpr int OOB = (int)0x80000000u;
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-__device__ u32x4 raw_buffer_load_v4(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4i32");
-__device__ void raw_buffer_store_v4(u32x4 data, i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v4i32");
-__device__ void raw_buffer_load_lds(i32x4 rsrc, __attribute__((address_space(3))) void* lds, int size, int voffset,
-                                    int soffset, int offset, int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
-
-__device__ __forceinline__ i32x4 rsrc_of(const void* base, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  i32x4 r;
-  r.x = (int)(unsigned)a;
-  r.y = (int)(unsigned)(a >> 32);
-  r.z = (int)bytes;
-  r.w = 0x00020000;
-  return r;
-}
-// an LDS read the compiler tracks (it places the lgkmcnt waits before the MFMAs that consume it)
-typedef const __attribute__((address_space(3))) u32x4 lds_u32x4;
-__device__ __forceinline__ u32x4 ds_read16(unsigned addr) { return *reinterpret_cast<lds_u32x4*>(addr); }
-__device__ __forceinline__ uint4 to_u4(u32x4 v) { return make_uint4(v.x, v.y, v.z, v.w); }
-
-template <typename T>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  typedef T t2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, t2{(T)a, (T)b});
-}
 
 // one workgroup's tile of layer p (bid: its index within the layer)
 template <typename T, int KPW>
@@ -77,8 +50,7 @@ __device__ __forceinline__ void burst_tile(const BurstParams& p, const int bid) 
   // XCD-aware order: contiguous runs of (pixel tile, channel tile) per XCD, the channel tiles of a
   // pixel tile adjacent (they stage the same input window: L2 hits)
   const int nbk = p.ptiles * p.ntiles;
-  const int q8 = nbk >> 3, r8 = nbk & 7, xcd = bid & 7;
-  const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int lin = xcd_linear(bid, nbk);
   const int nt = lin % p.ntiles, pt = lin / p.ntiles;
   const int fr = pt / p.tiles_pf;
   const int hw = p.Ho * p.Wo;
@@ -188,8 +160,8 @@ __device__ __forceinline__ void burst_tile(const BurstParams& p, const int bid) 
 #pragma unroll
     for (int t = 0; t < kBurstMaxSeg; ++t)
       if (t == s) a0 = abase[t][0], a1 = abase[t][1];
-    const u32x4 x0 = ds_read16(live ? a0 + off : zaddr);
-    const u32x4 x1 = ds_read16(live ? a1 + off : zaddr);
+    const u32x4 x0 = lds_load16(live ? a0 + off : zaddr);
+    const u32x4 x1 = lds_load16(live ? a1 + off : zaddr);
     Mfma<T>::run(to_u4(wreg[i]), to_u4(x0), acc0);
     Mfma<T>::run(to_u4(wreg[i]), to_u4(x1), acc1);
   }

@@ -34,23 +34,7 @@ constexpr int G = GA + GB;                   // LDS-DMA instructions per wave pe
 constexpr int SR = CH + 4;                   // staged fp32 row (floats)
 static_assert(PX * SR * 4 <= LDS - 16, "reduction tile fits the ring (below the split-K ticket word)");
 
-typedef __attribute__((address_space(3))) char lds_char;
-typedef const __attribute__((address_space(1))) void gvoid;
 typedef const __attribute__((address_space(4))) u32x4 c_u32x4;
-
-__device__ __forceinline__ void dma16(const void* src, lds_char* dst_wave_base) {
-  __builtin_amdgcn_global_load_lds((gvoid*)src, (__attribute__((address_space(3))) void*)dst_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ u32x4 ds_read16(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-  return v;
-}
-__device__ __forceinline__ uint4 to_u4(u32x4 v) { return make_uint4(v.x, v.y, v.z, v.w); }
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) unsigned gu32;  // global (never flat) agent-scope ticket words
-__device__ u32x4 raw_buffer_load_v4(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4i32");
-__device__ void raw_buffer_store_v4(u32x4 data, i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v4i32");
 
 // one workgroup's tile (or split-K slice of a tile) of the layer *pp; bid = its index in the layer
 template <typename T, bool X3 = false>  // X3: fp32 operands, products as three fp16 MFMAs (conv_pipe.hip X3)
@@ -73,8 +57,7 @@ __device__ __forceinline__ void conv_lat_tile(const ConvParams* __restrict__ pp,
   // (split-K: the ksplit slices of a tile adjacent too, so they tend to share an XCD — speed only)
   const int ksplit = p.ksplit > 1 ? p.ksplit : 1;
   const int nbk = p.mtiles * p.ntiles * ksplit;
-  const int q8 = nbk >> 3, r8 = nbk & 7, xcd = bid & 7;
-  const int lin_s = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int lin_s = xcd_linear(bid, nbk);
   const int lin = lin_s / ksplit;      // tile
   const int slice = lin_s - lin * ksplit;
   const int ntile = lin % p.ntiles;
@@ -300,15 +283,7 @@ __device__ __forceinline__ void conv_lat_tile(const ConvParams* __restrict__ pp,
     // ticket; the workgroup drawing ksplit - 1 sums every slice in slice order 0, 1, ... (its own
     // from registers, the others by sc1 loads: bit-identical whichever workgroup arrives last) and
     // resets the ticket. The engine also zeroes the tickets before each forward.
-    i32x4 rs;
-    {
-      const unsigned long long a = (unsigned long long)(p.slab + (size_t)lin * ksplit * (PX * CH));
-      rs.x = (int)(unsigned)a;
-      rs.y = (int)(unsigned)(a >> 32);
-      rs.z = ksplit * PX * CH * 4;
-      rs.w = 0x00020000;
-    }
-    constexpr int SC1 = 16;  // aux cache bits: sc1 (write-through store / L1-bypassing load)
+    const i32x4 rs = rsrc_of(p.slab + (size_t)lin * ksplit * (PX * CH), (unsigned)(ksplit * PX * CH * 4));
 #pragma unroll
     for (int r = 0; r < RPT; ++r) {
       const int it = tid + r * NT;
@@ -317,6 +292,7 @@ __device__ __forceinline__ void conv_lat_tile(const ConvParams* __restrict__ pp,
       raw_buffer_store_v4(__builtin_bit_cast(u32x4, xs[r][0]), rs, off, 0, SC1);
       raw_buffer_store_v4(__builtin_bit_cast(u32x4, xs[r][1]), rs, off + 16, 0, SC1);
     }
+    // splitk_arrive_is_last() written out: as a call, p.cnt is read before the drain, not by thread 0 alone
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave: its slab bytes landed
     __syncthreads();
     unsigned* last_flag = reinterpret_cast<unsigned*>(smem + LDS - 16);
@@ -338,8 +314,8 @@ __device__ __forceinline__ void conv_lat_tile(const ConvParams* __restrict__ pp,
         if (q != slice) {
           const int off = (q * (PX * CH) + it * 8) * 4;
           const bool live = m0 + (it >> 4) < p.M;
-          a0 = __builtin_bit_cast(f32x4, raw_buffer_load_v4(rs, live ? off : (int)0x80000000u, 0, SC1));
-          a1 = __builtin_bit_cast(f32x4, raw_buffer_load_v4(rs, live ? off + 16 : (int)0x80000000u, 0, SC1));
+          a0 = __builtin_bit_cast(f32x4, raw_buffer_load_v4(rs, live ? off : OOB, 0, SC1));
+          a1 = __builtin_bit_cast(f32x4, raw_buffer_load_v4(rs, live ? off + 16 : OOB, 0, SC1));
         }
         if (q == 0) {
           sum[r][0] = a0;
@@ -355,7 +331,7 @@ __device__ __forceinline__ void conv_lat_tile(const ConvParams* __restrict__ pp,
       xs[r][0] = sum[r][0];
       xs[r][1] = sum[r][1];
     }
-    if (tid == 0) __hip_atomic_store((gu32*)(p.cnt + lin), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    splitk_reset((gu32*)(p.cnt + lin));
   }
   // bias + activation + 16-byte stores: 64 pixels x 16 chunks of 8 channels, 2 per thread
   T* const out = reinterpret_cast<T*>(p.out);

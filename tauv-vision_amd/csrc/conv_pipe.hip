@@ -30,31 +30,6 @@ constexpr int GA = BM / 8 / NW;              // A pieces (1 KiB) per wave per k-
 constexpr int GB = BN / 8 / NW;              // B pieces per wave per k-step = 2
 constexpr int G = GA + GB;                   // LDS-DMA instructions per wave per k-step
 
-typedef __attribute__((address_space(3))) char lds_char;
-typedef const __attribute__((address_space(1))) void gvoid;
-typedef __attribute__((address_space(1))) unsigned gu32;  // global (never flat) agent-scope ticket words
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-__device__ u32x4 raw_buffer_load_v4(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4i32");
-__device__ void raw_buffer_store_v4(u32x4 data, i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v4i32");
-
-__device__ __forceinline__ void dma16(const void* src, lds_char* dst_wave_base) {
-  __builtin_amdgcn_global_load_lds((gvoid*)src, (__attribute__((address_space(3))) void*)dst_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ u32x4 ds_read16(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-  return v;
-}
-template <int OFF>
-__device__ __forceinline__ u32x4 ds_read16_off(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-
-__device__ __forceinline__ uint4 to_u4(u32x4 v) { return make_uint4(v.x, v.y, v.z, v.w); }
-
 // X3 (T = float only): fp32 operands, products as three fp16 MFMAs — a = a_hi + a_lo, b = b_hi + b_lo
 // with hi = fp16(x), lo = fp16(x - hi) (22 significant bits), a*b = a_hi*b_hi + a_hi*b_lo + a_lo*b_hi
 // (+ a_lo*b_lo ~ 2^-22 relative, dropped) accumulated in fp32: v_mfma_f32_32x32x16_f16 at 16x the
@@ -81,8 +56,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pipe(const ConvParams* __restrict_
   const int ksplit = p.ksplit > 1 ? p.ksplit : 1;
   const int nb = p.mtiles * p.ntiles * ksplit;
   const int bid = blockIdx.x;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-  const int lin_s = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int lin_s = xcd_linear(bid, nb);
   const int lin = lin_s / ksplit;
   const int slice = lin_s - lin * ksplit;
   const int ks0 = (int)((long)p.nks * slice / ksplit);
@@ -344,15 +318,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pipe(const ConvParams* __restrict_
     // (its own from LDS, the others by L1-bypassing sc1 loads: bit-identical whichever arrives
     // last), applies bias + activation, stores, and resets the ticket.
     constexpr int TILE_F = BM * BN;
-    constexpr int SC1 = 16;
-    i32x4 rs;
-    {
-      const unsigned long long a = (unsigned long long)(p.slab + (size_t)lin * ksplit * TILE_F);
-      rs.x = (int)(unsigned)a;
-      rs.y = (int)(unsigned)(a >> 32);
-      rs.z = ksplit * TILE_F * 4;
-      rs.w = 0x00020000;
-    }
+    const i32x4 rs = rsrc_of(p.slab + (size_t)lin * ksplit * TILE_F, (unsigned)(ksplit * TILE_F * 4));
     constexpr int FCPR = BN / 4, FRSTEP = NT / FCPR, FNP = BM / FRSTEP;
     const int fcc = tid % FCPR, fr0 = tid / FCPR;
 #pragma unroll
@@ -362,13 +328,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pipe(const ConvParams* __restrict_
       const f32x4 v = *reinterpret_cast<const f32x4*>(stg + row * SR + fcc * 4);
       raw_buffer_store_v4(__builtin_bit_cast(u32x4, v), rs, ((slice * BM + row) * BN + fcc * 4) * 4, 0, SC1);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    unsigned* last_flag = reinterpret_cast<unsigned*>(smem + LDS - 16);
-    if (tid == 0) *last_flag = __hip_atomic_fetch_add((gu32*)(p.cnt + lin), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (*last_flag != (unsigned)(ksplit - 1)) return;  // workgroup-uniform
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // compiler-only: every slab load below is sc1
+    if (!splitk_arrive_is_last((gu32*)(p.cnt + lin), ksplit, reinterpret_cast<unsigned*>(smem + LDS - 16))) return;
     const int nf = n0 + fcc * 4;
     const uint4 braw = gload16(p.bias + nf);
     const float bias4[4] = {__uint_as_float(braw.x), __uint_as_float(braw.y), __uint_as_float(braw.z),
@@ -406,7 +366,7 @@ __global__ __launch_bounds__(NT, 2) void conv_pipe(const ConvParams* __restrict_
       *reinterpret_cast<f32x4*>(stg + row * SR + fcc * 4) = f32x4{v[0], v[1], v[2], v[3]};
     }
     __syncthreads();
-    if (tid == 0) __hip_atomic_store((gu32*)(p.cnt + lin), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    splitk_reset((gu32*)(p.cnt + lin));
   }
   if (MODE == 0) {
     if (n < p.N) {

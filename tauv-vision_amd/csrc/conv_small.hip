@@ -39,12 +39,6 @@ template <> struct M16<__bf16> {
 
 constexpr int NT = 256;  // 4 waves
 
-template <typename T>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  typedef T t2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, t2{(T)a, (T)b});
-}
-
 template <typename T, int CIN, int COUT, int STRIDE, int ACT>
 __global__ __launch_bounds__(NT) void conv_small(const ConvParams* __restrict__ pp) {
   constexpr int NS = (9 * CIN + 31) / 32;  // K slabs of 32
@@ -120,7 +114,6 @@ __global__ __launch_bounds__(NT) void conv_small(const ConvParams* __restrict__ 
         else if constexpr (ACT == 2) t = fmaxf(t, 0.01f * t);
         v[r] = t;
       }
-      typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
       *reinterpret_cast<u32x2*>(dst + 16 * ob + 4 * g) = u32x2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
     }
   };
@@ -149,20 +142,6 @@ __global__ __launch_bounds__(NT) void conv_small(const ConvParams* __restrict__ 
 // MFMAs; no double buffering. On a persistent grid (variant 2) each workgroup keeps its weight
 // fragments in registers across the tiles of its XCD-contiguous range (variant 1: a tile per
 // workgroup, every one reloading the weights).
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-__device__ void raw_buffer_load_lds(i32x4 rsrc, __attribute__((address_space(3))) void* lds, int size, int voffset,
-                                    int soffset, int offset, int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
-__device__ __forceinline__ i32x4 rsrc_of(const void* base, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  i32x4 r;
-  r.x = (int)(unsigned)a;
-  r.y = (int)(unsigned)(a >> 32);
-  r.z = (int)bytes;
-  r.w = 0x00020000;
-  return r;
-}
-typedef const __attribute__((address_space(3))) u32x4 lds_u32x4;
-constexpr int OOB = (int)0x80000000u;
 
 template <int CIN, int STRIDE, int TW, int TR> struct HaloGeo {
   static constexpr int CPP = CIN / 8;                 // 16-byte chunks per input pixel
@@ -183,7 +162,6 @@ __global__ __launch_bounds__(NT) void conv_small_halo(const ConvParams* __restri
   constexpr int NS = (9 * CIN + 31) / 32;
   constexpr int NB = COUT / 16;
   __shared__ __attribute__((aligned(16))) char smem[G::LDS];
-  typedef __attribute__((address_space(3))) char lds_char;
   lds_char* lds = (lds_char*)smem;
   const ConvParams& p = *pp;
   const ConvSegment& sg = p.seg[0];
@@ -196,17 +174,8 @@ __global__ __launch_bounds__(NT) void conv_small_halo(const ConvParams* __restri
   const int ntiles = p.M / (Ho * Wo) * tiles_y * tiles_x;
   // XCD-aware: workgroup b runs on XCD b % 8, so each XCD walks a contiguous tile range (shared
   // halo rows in its L2); one tile per workgroup when the grid is the tile count, else persistent
-  const int nb = gridDim.x, bid = blockIdx.x;
-  int first, end, step;
-  if ((nb & 7) == 0) {
-    first = (int)((long long)ntiles * (bid & 7) / 8) + (bid >> 3);
-    end = (int)((long long)ntiles * ((bid & 7) + 1) / 8);
-    step = nb >> 3;
-  } else {
-    first = bid;
-    end = ntiles;
-    step = nb;
-  }
+  const XcdRange xr = xcd_range(ntiles);
+  const int first = xr.first, end = xr.end, step = xr.stride;
   const unsigned frame_bytes = (unsigned)H * W * ldc * (unsigned)sizeof(T);
   // stage tile t's halo: chunk q*64 + lane of the tile, pixel-major, CPP chunks per pixel
   auto stage = [&](int t) __attribute__((always_inline)) {
@@ -268,7 +237,7 @@ __global__ __launch_bounds__(NT) void conv_small_halo(const ConvParams* __restri
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         if (toff[s] >= 0) {
-          const u32x4 v = *reinterpret_cast<lds_u32x4*>(base + toff[s]);
+          const u32x4 v = lds_load16(base + toff[s]);
           b[s] = make_uint4(v.x, v.y, v.z, v.w);
         } else {
           b[s] = make_uint4(0, 0, 0, 0);
@@ -294,7 +263,6 @@ __global__ __launch_bounds__(NT) void conv_small_halo(const ConvParams* __restri
           else if constexpr (ACT == 2) y = fmaxf(y, 0.01f * y);
           v[e] = y;
         }
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         *reinterpret_cast<u32x2*>(dst + 16 * ob + 4 * g) = u32x2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
       }
     }

@@ -34,11 +34,6 @@ template <int NP>
 constexpr int lds_bytes() { return NP * (PW + C * 4); }
 
 template <typename T>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  typedef T t2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, t2{(T)a, (T)b});
-}
-template <typename T>
 __device__ __forceinline__ float lo_f(unsigned u) {
   return (float)__builtin_bit_cast(T, (uint16_t)(u & 0xffffu));
 }

@@ -28,7 +28,6 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 namespace tv {
@@ -47,7 +46,6 @@ constexpr int OFF_W = 2 * HBUF;
 constexpr int OFF_B = OFF_W + 2 * WBUF;
 constexpr int LDS = OFF_B + 2 * NCO * 4;  // (a bias slot per buffer set)
 static_assert(LDS <= 160 * 1024, "LDS budget");
-constexpr int OOB = (int)0x80000000u;
 #ifndef CT3_WD
 #define CT3_WD 8   // weight fragments in flight per wave (ring depth)
 #endif
@@ -59,23 +57,6 @@ constexpr int OOB = (int)0x80000000u;
 // packed weights use (taps grouped: tap 0 serves all 4 phases, taps 1 / 2 two, tap 3 one)
 constexpr int Q_PH[NQ] = {0, 1, 2, 3, 1, 3, 2, 3, 3};
 constexpr int Q_TAP[NQ] = {0, 0, 0, 0, 1, 1, 2, 2, 3};
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-__device__ void raw_buffer_store_v4(u32x4 data, i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v4i32");
-__device__ void raw_buffer_load_lds(i32x4 rsrc, __attribute__((address_space(3))) void* lds, int size, int voffset,
-                                    int soffset, int offset, int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
-
-__device__ __forceinline__ i32x4 rsrc_of(const void* base, unsigned bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  i32x4 r;
-  r.x = (int)(unsigned)a;
-  r.y = (int)(unsigned)(a >> 32);
-  r.z = (int)bytes;
-  r.w = 0x00020000;
-  return r;
-}
-typedef const __attribute__((address_space(3))) u32x4 lds_u32x4;
-__device__ __forceinline__ u32x4 lds16(unsigned addr) { return *reinterpret_cast<lds_u32x4*>(addr); }
 
 // conv3x3.hip's 16x16x32 lane permutation: fragment column n reads pixel pi(n), K group c reads
 // 16-byte chunk sigma(c) (ds_read_b128 lane groups on distinct 4-bank sets at the 80-byte pitch)
@@ -94,19 +75,9 @@ template <> struct Mf<__bf16> {
   }
 };
 
-template <typename T>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  typedef T t2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, t2{(T)a, (T)b});
-}
-
-template <int V>
-using IC = std::integral_constant<int, V>;
-
 template <typename T, int ACT>
 __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_eu(2, 2))) void convt3(ConvT3Params p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef __attribute__((address_space(3))) char lds_char;
   lds_char* lds = (lds_char*)smem;
   const unsigned lds0 = (unsigned)(uintptr_t)lds;
   const int tid = threadIdx.x;
@@ -122,17 +93,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   const int ncb = p.C / 32;
   const int nunits = p.B * tiles_y * tiles_x * nco;
   // XCD-aware contiguous unit ranges (the channel tiles of an input tile adjacent: the same halo)
-  const int G = gridDim.x, bid = blockIdx.x;
-  int first, stride, end;
-  if ((G & 7) == 0) {
-    first = (int)((long long)nunits * (bid & 7) / 8) + (bid >> 3);
-    end = (int)((long long)nunits * ((bid & 7) + 1) / 8);
-    stride = G >> 3;
-  } else {
-    first = bid;
-    end = nunits;
-    stride = G;
-  }
+  const XcdRange xr = xcd_range(nunits);
+  const int first = xr.first, end = xr.end, stride = xr.stride;
   if (first >= end) return;
   auto unit_of = [&](int u, int& fr, int& y0, int& x0, int& co) __attribute__((always_inline)) {
     co = u % nco;
@@ -240,16 +202,16 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
     constexpr int WD = CT3_WD;
     u32x4 X[4][2], Wr[WD];
 #pragma unroll
-    for (int i = 0; i < WD; ++i) Wr[i] = lds16(wb + (unsigned)(i * 1024));
+    for (int i = 0; i < WD; ++i) Wr[i] = lds_load16(wb + (unsigned)(i * 1024));
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
-      for (int f = 0; f < 2; ++f) X[t][f] = lds16(hb + xrel[f] + tapoff[t]);
+      for (int f = 0; f < 2; ++f) X[t][f] = lds_load16(hb + xrel[f] + tapoff[t]);
 #pragma unroll
     for (int i = 0; i < WPIECES; ++i) {
       const int q = i >> 2, c = i & 3;
       const u32x4 wf = Wr[i % WD];
-      if (i + WD < WPIECES) Wr[i % WD] = lds16(wb + (unsigned)((i + WD) * 1024));
+      if (i + WD < WPIECES) Wr[i % WD] = lds_load16(wb + (unsigned)((i + WD) * 1024));
 #pragma unroll
       for (int f = 0; f < 2; ++f) {
 #if defined(TV_CT3_EXP) && TV_CT3_EXP == 4
@@ -381,11 +343,7 @@ void convt3_pack(const float* w, int C, int N, int dtype, void* out) {
     if (dtype == F16) {
       reinterpret_cast<_Float16*>(out)[i] = (_Float16)v;
     } else {
-      uint32_t u;
-      std::memcpy(&u, &v, 4);
-      if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x7FFFFFu)) u = (u >> 16) | 0x40;
-      else u = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-      reinterpret_cast<uint16_t*>(out)[i] = (uint16_t)u;
+      reinterpret_cast<uint16_t*>(out)[i] = f32_to_bf16(v);
     }
   };
   for (int t = 0; t < nco; ++t)

@@ -31,19 +31,6 @@ template <int BN> constexpr int wbuf() { return BN * PITCH; }  // weight rows x 
 template <int BN> constexpr int lds_bytes() { return 2 * (ABUF + wbuf<BN>()); }
 constexpr int kOOB = 0x7ff00000;          // buffer offset past any num_records (host checks the sizes)
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) unsigned gu32;  // global (never flat) agent-scope ticket words
-__device__ u32x4 raw_buffer_load_v4(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4i32");
-__device__ void raw_buffer_store_v4(u32x4 data, i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v4i32");
-__device__ void raw_buffer_load_lds(i32x4 rsrc, __attribute__((address_space(3))) void* lds, int size, int voffset,
-                                    int soffset, int offset, int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
-__device__ __forceinline__ uint4 to_u4(u32x4 v) { return make_uint4(v.x, v.y, v.z, v.w); }
-
-template <typename T>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  typedef T t2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, t2{(T)a, (T)b});
-}
 // w * f16 (low / high half of v) [+ acc] in fp32
 __device__ __forceinline__ float mix_lo(float w, unsigned v) {
   float r;
@@ -101,13 +88,8 @@ __global__ __launch_bounds__(NT) void dcn_gemm(const DcnParams p) {
   // x and the weights through buffer resources: per tap, one byte offset per corner (an invalid
   // corner's offset lies past num_records, so its load returns zeros and the blend needs no
   // select), the channel block / k-step in the scalar offset
-  i32x4 xr, wrs;
-  {
-    const unsigned long long a = (unsigned long long)p.x, aw = (unsigned long long)p.w;
-    xr = i32x4{(int)(unsigned)a, (int)(unsigned)(a >> 32), (int)((unsigned)M * p.ldx * (unsigned)sizeof(T)), 0x00020000};
-    wrs = i32x4{(int)(unsigned)aw, (int)(unsigned)(aw >> 32), (int)((unsigned)p.N * p.Kpad * (unsigned)sizeof(T)),
-                0x00020000};
-  }
+  const i32x4 xr = rsrc_of(p.x, (unsigned)M * p.ldx * (unsigned)sizeof(T));
+  const i32x4 wrs = rsrc_of(p.w, (unsigned)p.N * p.Kpad * (unsigned)sizeof(T));
   const int xlane = (b * HW * p.ldx + 16 * h) * (int)sizeof(T);
 
   // per-tap sampling state (dcn_sample's expressions; the mask is folded into the corner weights)
@@ -255,7 +237,6 @@ __global__ __launch_bounds__(NT) void dcn_gemm(const DcnParams p) {
         else if (p.act == 2) t = fmaxf(t, 0.01f * t);
         v[e] = t;
       }
-      typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
       *reinterpret_cast<u32x2*>(dst + ch) = u32x2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
     }
 }
@@ -315,13 +296,8 @@ __global__ __launch_bounds__(NT, (min_blocks2<BN, PX>())) void dcn_gemm64(const 
   const int k_lo = 9 * slice / ksplit, k_hi = 9 * (slice + 1) / ksplit;
   const int S0 = k_lo * ncb, S = k_hi * ncb;
 
-  i32x4 xr, wrs;
-  {
-    const unsigned long long a = (unsigned long long)p.x, aw = (unsigned long long)p.w;
-    xr = i32x4{(int)(unsigned)a, (int)(unsigned)(a >> 32), (int)((unsigned)M * p.ldx * (unsigned)sizeof(T)), 0x00020000};
-    wrs = i32x4{(int)(unsigned)aw, (int)(unsigned)(aw >> 32), (int)((unsigned)p.N * p.Kpad * (unsigned)sizeof(T)),
-                0x00020000};
-  }
+  const i32x4 xr = rsrc_of(p.x, (unsigned)M * p.ldx * (unsigned)sizeof(T));
+  const i32x4 wrs = rsrc_of(p.w, (unsigned)p.N * p.Kpad * (unsigned)sizeof(T));
 
   // ---- sampling-state producer: thread tid < PX owns pixel tid (dcn_sample's expressions)
   const int pm = m0 + (tid & (PX - 1));
@@ -487,12 +463,8 @@ __global__ __launch_bounds__(NT, (min_blocks2<BN, PX>())) void dcn_gemm64(const 
     // workgroup barrier orders that before one relaxed agent-scope ticket; the workgroup drawing
     // ksplit - 1 sums every slice from the slab in slice order (sc1 loads, its own included:
     // bit-identical whichever arrives last), resets the ticket and runs the epilogue below
-    constexpr int SC1 = 16, PER = NA * 16;  // floats per thread
-    i32x4 rs;
-    {
-      const unsigned long long a = (unsigned long long)(p.slab + (size_t)unit * ksplit * NT * PER);
-      rs = i32x4{(int)(unsigned)a, (int)(unsigned)(a >> 32), ksplit * NT * PER * 4, 0x00020000};
-    }
+    constexpr int PER = NA * 16;  // floats per thread
+    const i32x4 rs = rsrc_of(p.slab + (size_t)unit * ksplit * NT * PER, (unsigned)(ksplit * NT * PER * 4));
     const int toff = tid * PER * 4;
 #pragma unroll
     for (int i = 0; i < NA; ++i)
@@ -501,6 +473,8 @@ __global__ __launch_bounds__(NT, (min_blocks2<BN, PX>())) void dcn_gemm64(const 
         raw_buffer_store_v4(u32x4{__float_as_uint(acc[i][4 * g]), __float_as_uint(acc[i][4 * g + 1]),
                                   __float_as_uint(acc[i][4 * g + 2]), __float_as_uint(acc[i][4 * g + 3])},
                             rs, toff + (i * 4 + g) * 16, slice * NT * PER * 4, SC1);
+    // splitk_arrive_is_last() / splitk_reset() written out: as calls, the ticket address is computed
+    // before the drain by every thread, not by thread 0 at each use
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     unsigned* last_flag = reinterpret_cast<unsigned*>(smem);  // (operand buffers: every read done)
@@ -547,7 +521,6 @@ __global__ __launch_bounds__(NT, (min_blocks2<BN, PX>())) void dcn_gemm64(const 
         else if (p.act == 2) t = fmaxf(t, 0.01f * t);
         v[e] = t;
       }
-      typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
       *reinterpret_cast<u32x2*>(dst + ch) = u32x2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
     }
 }
@@ -567,7 +540,6 @@ template <int BN, int PX> constexpr int lds_bytes2d() { return 2 * (abuf2<PX>() 
 template <int BN, int PX> constexpr int min_blocks2d() {
   return 160 * 1024 / lds_bytes2d<BN, PX>() < 3 ? 160 * 1024 / lds_bytes2d<BN, PX>() : 3;
 }
-__device__ unsigned raw_buffer_load_u32(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.i32");
 template <typename T>
 __device__ __forceinline__ float half_of(unsigned v, int hi) {
   const uint16_t b = (uint16_t)(hi ? v >> 16 : v & 0xffffu);
@@ -596,15 +568,9 @@ __global__ __launch_bounds__(NT, (min_blocks2d<BN, PX>())) void dcn_gemm64d(cons
   const int ncb = p.C / 64;
   const int S = 9 * ncb;
 
-  i32x4 xr, wrs, omr;
-  {
-    const unsigned long long a = (unsigned long long)p.x, aw = (unsigned long long)p.w, ao = (unsigned long long)p.om;
-    xr = i32x4{(int)(unsigned)a, (int)(unsigned)(a >> 32), (int)((unsigned)M * p.ldx * (unsigned)sizeof(T)), 0x00020000};
-    wrs = i32x4{(int)(unsigned)aw, (int)(unsigned)(aw >> 32), (int)((unsigned)p.N * p.Kpad * (unsigned)sizeof(T)),
-                0x00020000};
-    omr = i32x4{(int)(unsigned)ao, (int)(unsigned)(ao >> 32), (int)((unsigned)M * p.om_ldc * (unsigned)sizeof(T)),
-                0x00020000};
-  }
+  const i32x4 xr = rsrc_of(p.x, (unsigned)M * p.ldx * (unsigned)sizeof(T));
+  const i32x4 wrs = rsrc_of(p.w, (unsigned)p.N * p.Kpad * (unsigned)sizeof(T));
+  const i32x4 omr = rsrc_of(p.om, (unsigned)M * p.om_ldc * (unsigned)sizeof(T));
 
   // ---- sampling-state producer: thread tid < PX owns pixel tid (dcn_sample's expressions)
   const int pm = m0 + (tid & (PX - 1));
@@ -784,7 +750,6 @@ __global__ __launch_bounds__(NT, (min_blocks2d<BN, PX>())) void dcn_gemm64d(cons
         else if (p.act == 2) t = fmaxf(t, 0.01f * t);
         v[e] = t;
       }
-      typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
       *reinterpret_cast<u32x2*>(dst + ch) = u32x2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
     }
 }
@@ -850,25 +815,11 @@ __global__ __attribute__((amdgpu_flat_work_group_size(win::WNT, win::WNT), amdgp
   const int tiles_x = (W + TW - 1) / TW, tiles_f = ((H + TH - 1) / TH) * tiles_x;
   const int ntot = p.B * tiles_f;
   // XCD-aware contiguous tile ranges (neighbouring tiles share window rows in the XCD's L2)
-  const int G = gridDim.x, bid = blockIdx.x;
-  int first, stride, end;
-  if ((G & 7) == 0) {
-    first = (int)((long long)ntot * (bid & 7) / 8) + (bid >> 3);
-    end = (int)((long long)ntot * ((bid & 7) + 1) / 8);
-    stride = G >> 3;
-  } else {
-    first = bid;
-    end = ntot;
-    stride = G;
-  }
+  const XcdRange xcr = xcd_range(ntot);
+  const int first = xcr.first, end = xcr.end, stride = xcr.stride;
   if (first >= end) return;
 
-  i32x4 xr;
-  {
-    const unsigned long long a = (unsigned long long)p.x;
-    xr = i32x4{(int)(unsigned)a, (int)(unsigned)(a >> 32),
-               (int)((unsigned)p.B * H * W * p.ldx * (unsigned)sizeof(T)), 0x00020000};
-  }
+  const i32x4 xr = rsrc_of(p.x, (unsigned)p.B * H * W * p.ldx * (unsigned)sizeof(T));
   auto dma = [&](int off, int lds_off) __attribute__((always_inline)) {
     raw_buffer_load_lds(xr, (__attribute__((address_space(3))) void*)(smem + lds_off), 16, off, 0, 0, 0);
   };
@@ -909,12 +860,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(win::WNT, win::WNT), amdgp
   // the 27 offset / mask values of this lane's pixel of tile t (32 fp16 = 4 x 16 B: om_ldc >= 32,
   // 16-byte rows), loaded a tile ahead with the window
   const int q = 32 * wave + l32;  // this lane's tile pixel
-  i32x4 omr;
-  {
-    const unsigned long long a = (unsigned long long)p.om;
-    omr = i32x4{(int)(unsigned)a, (int)(unsigned)(a >> 32),
-                (int)((unsigned)p.B * H * W * p.om_ldc * (unsigned)sizeof(T)), 0x00020000};
-  }
+  const i32x4 omr = rsrc_of(p.om, (unsigned)p.B * H * W * p.om_ldc * (unsigned)sizeof(T));
   uint4 omv[4];
   auto load_om = [&](int t) __attribute__((always_inline)) {
     const int fr = t / tiles_f, r = t - fr * tiles_f, ty = r / tiles_x;
@@ -1088,7 +1034,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(win::WNT, win::WNT), amdgp
             else if (p.act == 2) tt = fmaxf(tt, 0.01f * tt);
             v[e] = tt;
           }
-          typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
           *reinterpret_cast<u32x2*>(dst + ch) = u32x2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
         }
     }
@@ -1097,7 +1042,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(win::WNT, win::WNT), amdgp
 #if defined(TV_DCN_STAMPS)
   __syncthreads();
   if (lane == 0) {  // (the stamp build overwrites the output's first bytes)
-    unsigned long long* d = reinterpret_cast<unsigned long long*>(p.out) + ((size_t)bid * 8 + wave) * 8;
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(p.out) + ((size_t)blockIdx.x * 8 + wave) * 8;
 #pragma unroll
     for (int k = 0; k < 8; ++k) d[k] = st_b[k];
   }

@@ -18,7 +18,7 @@
 // in score resolve toward the smaller flat index (torch.topk: unspecified, decode.py:269).
 //
 //  peaks       : heatmap_nms() as a dense map (tv_heatmap_nms, parity API only).
-#include "common.h"
+#include "conv_common.h"
 
 #include <algorithm>
 #include <vector>
@@ -549,25 +549,12 @@ struct ScanWs {
   uint32_t N;         // C * H * W
 };
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-__device__ void raw_buffer_store_v2(u32x2 data, i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v2i32");
-__device__ u32x2 raw_buffer_load_v2(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v2i32");
-constexpr int kSC1 = 16;  // aux cache bits: sc1 (write-through store / L1- and L2-coherent load)
-typedef __attribute__((address_space(1))) uint32_t gu32;
-
 // the image's key array as a buffer resource (keys at 8-byte offsets)
 __device__ __forceinline__ i32x4 keys_rsrc(const ScanWs& w, int b) {
-  const unsigned long long a = (unsigned long long)(w.keys + (size_t)b * w.tiles * kScanElems);
-  i32x4 r;
-  r.x = (int)(unsigned)a;
-  r.y = (int)(unsigned)(a >> 32);
-  r.z = (int)((unsigned)w.tiles * kScanElems * 8u);
-  r.w = 0x00020000;
-  return r;
+  return rsrc_of(w.keys + (size_t)b * w.tiles * kScanElems, (unsigned)w.tiles * kScanElems * 8u);
 }
 __device__ __forceinline__ uint64_t load_key(const i32x4& rs, int i) {
-  const u32x2 v = raw_buffer_load_v2(rs, i * 8, 0, kSC1);
+  const u32x2 v = raw_buffer_load_v2(rs, i * 8, 0, SC1);
   return ((uint64_t)v.y << 32) | v.x;
 }
 
@@ -1090,7 +1077,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(5,
     }
     if (keep)
       raw_buffer_store_v2(u32x2{(uint32_t)key, (uint32_t)(key >> 32)}, krs,
-                          (int)((pos + wo + (uint32_t)__popcll(bal & lt)) * 8u), 0, kSC1);
+                          (int)((pos + wo + (uint32_t)__popcll(bal & lt)) * 8u), 0, SC1);
     pos += tot;
     // (raw barriers: the stores drain once, at the hand-off below)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");

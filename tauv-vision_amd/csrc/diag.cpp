@@ -11,14 +11,6 @@
 
 namespace {
 
-uint16_t to_bf16(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x7FFFFFu)) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
 void put(std::vector<uint8_t>& buf, size_t i, float v, int dtype) {
   if (dtype == tv::F32) {
     std::memcpy(buf.data() + 4 * i, &v, 4);
@@ -26,7 +18,7 @@ void put(std::vector<uint8_t>& buf, size_t i, float v, int dtype) {
     const _Float16 h = (_Float16)v;
     std::memcpy(buf.data() + 2 * i, &h, 2);
   } else {
-    const uint16_t b = to_bf16(v);
+    const uint16_t b = tv::f32_to_bf16(v);
     std::memcpy(buf.data() + 2 * i, &b, 2);
   }
 }

@@ -13,14 +13,6 @@ namespace tv {
 
 namespace {
 
-uint16_t f32_to_bf16(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x7FFFFFu)) return (uint16_t)((u >> 16) | 0x40);  // NaN
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
 void store_elem(void* base, size_t i, float v, int dtype) {
   if (dtype == F32) {
     reinterpret_cast<float*>(base)[i] = v;

@@ -54,21 +54,6 @@ template <int NI> struct Lay {
 __constant__ float kMean[3] = {0.485f, 0.456f, 0.406f};
 __constant__ float kStd[3] = {0.229f, 0.224f, 0.225f};
 
-template <typename T>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  typedef T t2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, t2{(T)a, (T)b});
-}
-
-// Workgroup barrier for LDS hand-offs only. __syncthreads() also waits for every outstanding
-// global store (vmcnt(0)), which would drain a tile's 128 KiB of stores before the next tile's
-// work instead of letting them stream under it.
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 // input staging modes: 0 normalised fp32 NCHW, 1 u8 HWC (any width), 2 u8 HWC with in_w % 4 == 0
 // (whole rows are dword aligned: the window is read as 30 dwords per row)
 template <int MODE> struct Window;

@@ -143,49 +143,7 @@ template <> struct Win<2> { static constexpr int DW = 54, NS = (WR * 54 + NT - 1
 __constant__ float kMean[3] = {0.485f, 0.456f, 0.406f};
 __constant__ float kStd[3] = {0.229f, 0.224f, 0.225f};
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-__device__ u32x4 raw_buffer_load_v4(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4i32");
-__device__ unsigned raw_buffer_load_u32(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.i32");
-__device__ unsigned char raw_buffer_load_u8(i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.i8");
-__device__ void raw_buffer_store_v4(u32x4 data, i32x4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.store.v4i32");
-
-constexpr int OOB = (int)0x80000000u;  // a buffer offset past every resource: loads 0, stores dropped
-
-__device__ __forceinline__ i32x4 rsrc_of(const void* base, unsigned long long bytes) {
-  const unsigned long long a = (unsigned long long)base;
-  i32x4 r;
-  r.x = (int)(unsigned)a;
-  r.y = (int)(unsigned)(a >> 32);
-  r.z = (int)(unsigned)bytes;
-  r.w = 0x00020000;
-  return r;
-}
-
-template <int OFF>
-__device__ __forceinline__ u32x4 ds_read16(unsigned addr) {
-  u32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-__device__ __forceinline__ uint4 to_u4(u32x4 v) { return make_uint4(v.x, v.y, v.z, v.w); }
-
-template <int V>
-using IC = std::integral_constant<int, V>;
-template <int Q, int N, typename F>
-__device__ __forceinline__ void unroll(F& f) {
-  if constexpr (Q < N) {
-    f(IC<Q>{});
-    unroll<Q + 1, N>(f);
-  }
-}
-
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-template <typename T>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  typedef T t2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, t2{(T)a, (T)b});
-}
 
 struct Half {     // conv1 fragments of one 16-deep sub-step
   u32x4 x[RPW];   // pixel fragments: tile rows 4w + f
@@ -203,12 +161,6 @@ __device__ __forceinline__ int opaque(int v) {
   return v;
 }
 
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 template <typename T, int MODE>
 __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_eu(2, 2))) void stem_s2(StemS2Params p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -223,17 +175,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   const int ntot = p.B * tiles_f;
 
   // ---- this block's tiles: XCD-aware contiguous ranges (conv3x3s2.hip)
-  const int G = gridDim.x, bid = blockIdx.x;
-  int first, stride, end;
-  if ((G & 7) == 0) {
-    first = (int)((long long)ntot * (bid & 7) / 8) + (bid >> 3);
-    end = (int)((long long)ntot * ((bid & 7) + 1) / 8);
-    stride = G >> 3;
-  } else {
-    first = bid;
-    end = ntot;
-    stride = G;
-  }
+  const XcdRange xr = xcd_range(ntot);
+  const int first = xr.first, end = xr.end, stride = xr.stride;
   const int ntl = first < end ? (end - first + stride - 1) / stride : 0;
   if (ntl == 0) return;
 #if TV_C3_EXP == 9
@@ -277,7 +220,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   unsigned raw[NS];
   auto load_window = [&](int fr, int oy0, int ox0) __attribute__((always_inline)) {
     const int wy0 = 2 * oy0 - 4, wx0 = 2 * ox0 - 4;
-    const i32x4 rs = rsrc_of((const char*)p.input + (size_t)fr * in_frame, in_frame);
+    const i32x4 rs = rsrc_of((const char*)p.input + (size_t)fr * in_frame, (unsigned)in_frame);
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
       const int idx = opaque(tid) + k * NT;
@@ -368,7 +311,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   // ---- stem weights of one channel block: A-fragments (32 channels x 16 K per k-step), one
   // 16-byte load per k-step per lane (stem_fragment_order; L2-resident), through a buffer resource
   uint4 wst[KS];
-  const i32x4 srsrc = rsrc_of(p.stem_w, (unsigned long long)KS * 4 * 1024);
+  const i32x4 srsrc = rsrc_of(p.stem_w, (unsigned)(KS * 4 * 1024));
   auto load_stem_w = [&](int cb) __attribute__((always_inline)) {
 #pragma unroll
     for (int j = 0; j < KS; ++j) wst[j] = to_u4(raw_buffer_load_v4(srsrc, lane * 16, (j * 4 + cb) * 1024, 0));
@@ -449,7 +392,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   // set q % 4, written to ring slot q % 3 at step q - 2; [k-step][128 rows][4 x 16 B] (stem_s2_repack)
   int wc_in = 0;
   WReg wreg[4];
-  const i32x4 wrsrc = rsrc_of(p.w1, (unsigned long long)SPT * WSLOT);
+  const i32x4 wrsrc = rsrc_of(p.w1, (unsigned)(SPT * WSLOT));
   const int wvoff = tid * WPL;
   auto w_load = [&](WReg& dst) __attribute__((always_inline)) {
     dst.a = raw_buffer_load_v4(wrsrc, wvoff, wc_in * WSLOT, 0);
@@ -469,8 +412,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   auto read_one = [&](auto r, auto sj, auto kj, unsigned xb, unsigned wb, Half& F) __attribute__((always_inline)) {
     constexpr int R = decltype(r)::value, SJ = decltype(sj)::value, KJ = decltype(kj)::value;
     constexpr int TOFF = (J_TY[KJ] * RS + J_TX[KJ]) * PITCH;
-    if constexpr (R < RPW) F.x[R] = ds_read16<TOFF + 32 * SJ + R * FOFF>(xb);
-    else F.w[R - RPW] = ds_read16<(R - RPW) * 2048>(wb);
+    if constexpr (R < RPW) F.x[R] = ds_read16_off<TOFF + 32 * SJ + R * FOFF>(xb);
+    else F.w[R - RPW] = ds_read16_off<(R - RPW) * 2048>(wb);
   };
   f32x16 acc[RPW][4];
   // the RPW MFMAs of channel fragment I (all pixel fragments)
@@ -488,7 +431,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   const unsigned long long res_frame = (unsigned long long)Ho * Wo * p.res_ldc * sizeof(T);
   auto copy_res = [&](auto cbc, int fr, int oy0, int ox0) __attribute__((always_inline)) {
     constexpr int CB = decltype(cbc)::value;
-    const i32x4 rs = rsrc_of((const char*)p.res + (size_t)fr * res_frame, res_frame);
+    const i32x4 rs = rsrc_of((const char*)p.res + (size_t)fr * res_frame, (unsigned)res_frame);
 #pragma unroll
     for (int k = 0; k < TH * TW * 4 / NT; ++k) {
       const int g = opaque(tid) + k * NT;
@@ -601,7 +544,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   const unsigned long long out_frame = (unsigned long long)Ho * Wo * p.out_ldc * sizeof(T);
   auto epilogue = [&](int fr, int oy0, int ox0) __attribute__((always_inline)) {
     const float* lb1 = reinterpret_cast<const float*>(smem + OFF_B1);
-    const i32x4 ors = rsrc_of((const char*)p.out + (size_t)fr * out_frame, out_frame);
+    const i32x4 ors = rsrc_of((const char*)p.out + (size_t)fr * out_frame, (unsigned)out_frame);
 #pragma unroll
     for (int f = 0; f < RPW; ++f) {
       const int y = oy0 + RPW * wave + f, x = ox0 + l32;
@@ -648,7 +591,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   auto block = [&](auto bc) __attribute__((always_inline)) {
     constexpr int B = decltype(bc)::value;
     SS2_STAMP(6);
-    lds_barrier();  // the previous block's k-steps have read the halo
+    lds_barrier_sched();  // the previous block's k-steps have read the halo
     SS2_STAMP(0);
     stem_phase(IC<B>{}, cur_y0, cur_x0);
     if constexpr (blk_p(B) == 1) load_stem_w(blk_cb((B + 1) % NBLK));  // lands under this block's k-steps
@@ -661,7 +604,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
   };
   if constexpr (MODE == 2) {  // the first tile's N and E (later tiles': under the previous tile)
     store_window(cur_y0, cur_x0);
-    lds_barrier();
+    lds_barrier_sched();
     expand(IC<1>{}, 0, 1);
   }
   for (int tl = 0; tl < ntl; ++tl) {
@@ -669,7 +612,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
     if constexpr (MODE != 2) {
       load_window(cur_fr, cur_y0, cur_x0);
       store_window(cur_y0, cur_x0);  // N was last read by expand<0> in the previous tile
-      lds_barrier();
+      lds_barrier_sched();
       expand(IC<1>{}, 0, 1);         // E was last read by block 15's stem phase
     }
     unroll<0, 8>(block);
@@ -682,7 +625,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
     cur_fr = nx_fr;
     cur_y0 = nx_y0;
     cur_x0 = nx_x0;
-    lds_barrier();  // block 15's k-steps are done with the halo / E before the next tile's writes
+    lds_barrier_sched();  // block 15's k-steps are done with the halo / E before the next tile's writes
   }
 #if TV_C3_EXP == 9
   SS2_STAMP(6);
