@@ -185,6 +185,19 @@ int tv_engine_forward_multi(tv_engine* engine, const float* const* inputs, int32
 int tv_engine_profile_multi(tv_engine* engine, const float* const* inputs, int32_t n_in, float* const* outputs,
                             int32_t n_out, int32_t batch, void* stream, float* ms, double* flops, int32_t cap,
                             int32_t* n_ops);
+/* tv_engine_forward_multi from raw u8 RGB camera frames NHWC [batch, in_h, in_w, 3] (any byte alignment)
+ * with T.ToTensor + T.Normalize(ImageNet) fused into the first kernel (yolact_node.py:109-119 at the
+ * model size: TV_ARCH_YOLACT, TV_ARCH_RESNET18; any arch whose one input is the image). A batch that runs
+ * as concurrent slices advances the frame pointer by in_h * in_w * 3 bytes per frame. An arch that takes
+ * feature maps (TV_ARCH_PROTONET, TV_ARCH_YOLACT_HEAD / _FPN) returns TV_EINVAL before any launch. */
+int tv_engine_forward_multi_u8(tv_engine* engine, const uint8_t* frames_nhwc, int32_t batch, float* const* outputs,
+                               int32_t n_out, void* stream);
+/* tv_engine_profile_multi and tv_engine_op_outputs_multi over the same u8 frames (yolact_node.py:109-119);
+ * tv_engine_op_kernel then names the kernel instances this input kind ran. */
+int tv_engine_profile_multi_u8(tv_engine* engine, const uint8_t* frames_nhwc, int32_t batch, float* const* outputs,
+                               int32_t n_out, void* stream, float* ms, double* flops, int32_t cap, int32_t* n_ops);
+int tv_engine_op_outputs_multi_u8(tv_engine* engine, const uint8_t* frames_nhwc, int32_t batch,
+                                  float* const* outputs, int32_t n_out, void* stream, void* const* dst, int32_t n_dst);
 /* Same from raw u8 RGB frames with ToTensor + Normalize fused (centernet_node.py:90-92). */
 int tv_engine_forward_u8(tv_engine* engine, const uint8_t* frames_nhwc, int32_t batch, float* out_nhwc,
                          void* stream);
@@ -214,8 +227,9 @@ int tv_engine_forward_insitu(tv_engine* engine, const float* img_nchw, int32_t b
 const char* tv_engine_op_label(tv_engine* engine, int32_t index);
 /* What op `index` launches in a `batch`-frame workspace (its route): the kernel instance as a
  * profiler demangles it, e.g. "tv::c3::conv3x3<_Float16, _Float16, 32, 1, 0, 0, 4, 4, 8>" (a
- * split-K launch with " split-K n" appended; the stem kernels' input-mode argument follows the last
- * profiled input kind), "prep" for the staging launch, or a parenthesised note for an op done
+ * split-K launch with " split-K n" appended; the stem kernels' input-mode argument — the last one of
+ * stem_conv, stem_s2 and stem7s2_pool, 0 for the fp32 image — follows the input kind of the last
+ * profile or op-outputs call), "prep" for the staging launch, or a parenthesised note for an op done
  * inside another op's launch, e.g. "(fused into the 3x3 heads)". "" before the batch's workspace
  * exists or past the last op. Diagnostic (roofline attribution, route table test). */
 const char* tv_engine_op_kernel(tv_engine* engine, int32_t batch, int32_t index);
@@ -333,6 +347,21 @@ int tv_yolact_assemble_masks_indexed(const float* mask_prototype, const int64_t 
                                      int32_t K, int32_t H, int32_t W, const float* mask_coeff, const float* box,
                                      int32_t A, const int64_t* det, const int32_t* counts, int32_t n_max, float* mask,
                                      void* stream);
+
+/* The node's per-detection outputs for the kept anchors of B images in one launch (yolact_node.py:129
+ * F.softmax(classification), :139-141 classification_max / confidence of the detections): classification
+ * [B,A,C+1] logits, box [B,A,4], det [B][n_max] int64 and counts [B] int32 as written by
+ * tv_yolact_fast_nms_batched -> records [B][n_max][8] fp32 (16-byte aligned): the anchor index, the
+ * class id (argmax of the logits over all C+1 columns, column 0 the background, the lowest index on an
+ * exact tie), the softmax probability of that class, the largest foreground probability (max over
+ * columns 1..C: the value nms.py:10 ranks by), the box y, x, h, w copied bit for bit. confidence (may be
+ * NULL) [B][n_max][C+1]: the whole softmax row. Softmax in fp32, max-subtracted. Every row of both
+ * outputs is written by every call; rows d >= counts[b] are zero. TV_EINVAL before any launch: null
+ * pointers, A < 1 or A > 2^24 (the index would not be exact in fp32), C+1 < 2. B * n_max == 0 succeeds
+ * and launches nothing. */
+int tv_yolact_detection_records(const float* classification, const float* box, const int64_t* det,
+                                const int32_t* counts, int32_t B, int32_t A, int32_t n_classes_with_bg, int32_t n_max,
+                                float* records, float* confidence, void* stream);
 
 /* Depth localisation of detections: the per-detection loops of the two reference nodes that turn
  * a detection into a camera-frame point, on the raw mono16 depth image. Device pointers, async on

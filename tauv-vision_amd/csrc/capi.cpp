@@ -104,6 +104,51 @@ int tv_engine_forward_multi(tv_engine* e, const float* const* inputs, int32_t n_
   })
 }
 
+// u8 camera frames feed only a plan whose one input is the image (staged by its first op); the archs
+// that take feature maps (OP_LAYOUT_IN) refuse them before anything is launched
+static int takes_frames(const Plan& p) {
+  bool ok = p.ins.size() == 1;
+  for (const OpSpec& op : p.ops) ok = ok && op.kind != OP_LAYOUT_IN;
+  if (!ok) set_error("this model takes an fp32 NCHW feature map, not u8 frames");
+  return ok ? TV_OK : TV_EINVAL;
+}
+
+int tv_engine_forward_multi_u8(tv_engine* e, const uint8_t* frames, int32_t B, float* const* outputs, int32_t n_out,
+                               void* stream) {
+  TV_GUARD({
+    if (!e) { set_error("null engine"); return TV_EINVAL; }
+    int rc = takes_frames(e->e.plan);
+    if (rc) return rc;
+    const void* in = frames;
+    return e->e.forward_multi(&in, 1, outputs, n_out, 1, B, (hipStream_t)stream);
+  })
+}
+
+int tv_engine_op_outputs_multi_u8(tv_engine* e, const uint8_t* frames, int32_t B, float* const* outputs, int32_t n_out,
+                                  void* stream, void* const* dst, int32_t n_dst) {
+  TV_GUARD({
+    if (!e || (n_dst > 0 && !dst) || n_dst < 0) { set_error("bad argument"); return TV_EINVAL; }
+    int rc = takes_frames(e->e.plan);
+    if (rc) return rc;
+    const void* in = frames;
+    return e->e.op_outputs_multi(&in, 1, outputs, n_out, 1, B, (hipStream_t)stream, dst, n_dst);
+  })
+}
+
+int tv_engine_profile_multi_u8(tv_engine* e, const uint8_t* frames, int32_t B, float* const* outputs, int32_t n_out,
+                               void* stream, float* ms, double* flops, int32_t cap, int32_t* n_ops) {
+  TV_GUARD({
+    if (!e || !ms || !flops || !n_ops) { set_error("null argument"); return TV_EINVAL; }
+    int rc = takes_frames(e->e.plan);
+    if (rc) return rc;
+    const void* in = frames;
+    int n = 0;
+    rc = e->e.profile_multi(&in, 1, outputs, n_out, 1, B, (hipStream_t)stream, ms, flops, cap, &n);
+    *n_ops = n;
+    return rc;
+  })
+}
+
 int tv_engine_profile_multi(tv_engine* e, const float* const* inputs, int32_t n_in, float* const* outputs,
                             int32_t n_out, int32_t B, void* stream, float* ms, double* flops, int32_t cap,
                             int32_t* n_ops) {
@@ -431,6 +476,12 @@ int tv_yolact_assemble_masks_indexed(const float* proto, const int64_t pst[4], i
     return launch_yolact_assemble_mask(proto, st, B, K, H, W, coeff, box, counts, (const long long*)det, A, n_max,
                                        mask, (hipStream_t)stream);
   })
+}
+
+int tv_yolact_detection_records(const float* cls, const float* box, const int64_t* det, const int32_t* counts, int32_t B,
+                                int32_t A, int32_t C1, int32_t n_max, float* records, float* confidence, void* stream) {
+  TV_GUARD({ return launch_yolact_detection_records(cls, box, (const long long*)det, counts, B, A, C1, n_max, records,
+                                                    confidence, (hipStream_t)stream); })
 }
 
 int tv_localize_boxes(const float* records, int32_t rec_stride, const int32_t* counts, int32_t B, int32_t K,

@@ -389,6 +389,13 @@ int launch_yolact_fast_nms(const float* cls, long long cls_bstride, int A, int C
 int launch_yolact_assemble_mask(const float* proto, const long long pst[4], int B, int K, int H, int W,
                                 const float* coeff, const float* box, const int* counts, const long long* det,
                                 int rows, int n_max, float* out, hipStream_t s);
+// The kept detections of B images as records (yolact_node.py:129,139-141): cls [B][A][C1] logits, box
+// [B][A][4], det [B][n_max] / counts [B] as the batched NMS writes them -> records [B][n_max][8] (anchor,
+// class id, its softmax probability, the largest foreground probability, y, x, h, w) and, when not
+// null, confidence [B][n_max][C1] (the softmax row); rows at or past counts[b] are zero. Arguments are
+// checked here (return 1 with the error text set); B * n_max == 0 launches nothing.
+int launch_yolact_detection_records(const float* cls, const float* box, const long long* det, const int* counts, int B,
+                                    int A, int C1, int n_max, float* records, float* confidence, hipStream_t s);
 // YOLACT neck and head (yolact_head.hip).
 // dst += bilinear(src -> dst's size), F.interpolate(mode="bilinear", align_corners=False), in place:
 // NHWC compute dtype, C channels and both pixel strides in whole 16-byte vectors
@@ -415,14 +422,16 @@ int launch_maxpool3x3s2(const void* src, int B, int H, int W, int C, void* out, 
 // out = relu(a + b) over n elements (fp32 sum, one rounding); out overlaps neither input
 int launch_add_relu(const void* a, const void* b, void* out, long long n, int dtype, hipStream_t s);
 // conv1 7x7 / s2 / p3 (3 -> 64, BatchNorm folded) + ReLU + MaxPool2d(3, 2, 1) in one launch, fp16 / bf16:
-// img fp32 NCHW [B, 3, H, W]; w [>= 64][Kpad] compute dtype in the engine's row-expanded stem packing
+// img fp32 NCHW [B, 3, H, W], or (u8 != 0) u8 NHWC camera frames [B, H, W, 3] at any byte alignment, ToTensor +
+// ImageNet Normalize applied as prep_u8 does; w [>= 64][Kpad] compute dtype in the engine's row-expanded stem packing
 // (K = ky * 24 + kx * 3 + c, zero elsewhere); bias fp32 [64]; out NHWC [B, PH, PW, 64], PH = ((H - 1) / 2 + 1 - 1) / 2 + 1
 struct StemPoolParams {
-  const float* img;
+  const void* img;
   const void* w;
   const float* bias;
   void* out;
   int B, H, W, Kpad;
+  int u8 = 0;
 };
 int launch_stem7s2_pool(const StemPoolParams& p, int dtype, int cu_count, hipStream_t s);// n compute-dtype elements -> fp32, exactly
 int launch_store_f32(const void* src, float* out, long long n, int dtype, hipStream_t s);

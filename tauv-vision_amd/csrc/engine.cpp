@@ -660,12 +660,9 @@ int Engine::run_op(size_t i, Workspace* ws, const IoPtrs& io, int input_u8, hipS
       return TV_OK;
     case Route::StemPool: {
       const Packed& pk = packed[rstem_op];
-      const StemPoolParams sp{(const float*)io.in[plan.ops[rstem_op - 1].io], pk.w, pk.bias, base + ws->off[op.out],
-                              ws->B, desc.in_h, desc.in_w, pk.Kpad};
-      if (input_u8) {
-        set_error("this model takes the normalised fp32 NCHW image, not u8 frames");
-        return TV_EINVAL;
-      }
+      // (u8 NHWC camera frames: the kernel's LUT instance, ToTensor + Normalize as launch_prep_u8's)
+      const StemPoolParams sp{io.in[plan.ops[rstem_op - 1].io], pk.w, pk.bias, base + ws->off[op.out],
+                              ws->B, desc.in_h, desc.in_w, pk.Kpad, input_u8 ? 1 : 0};
       return launch_stem7s2_pool(sp, dtype, cu_count, s);
     }
     case Route::Staging: {
@@ -1048,7 +1045,7 @@ const char* Engine::op_kernel(int B, size_t i) {
       case Route::MaxPool3S2: name = "tv::rn::maxpool3x3s2<" + t + ">"; break;
       case Route::AddRelu: name = "tv::rn::add_relu<" + t + ">"; break;
       case Route::StoreF32: name = "tv::rn::store_f32<" + t + ">"; break;
-      case Route::StemPool: name = "tv::rn::stem7s2_pool<" + t + ">"; break;
+      case Route::StemPool: name = "tv::rn::stem7s2_pool<" + t + ", " + (profiled_u8 ? "1>" : "0>"); break;
       case Route::StemInPool: name = "(fused into the max-pool: stem7s2_pool)"; break;
       case Route::DcnSample: name = "tv::dla::dcn_sample<" + t + ">"; break;
       case Route::DwConvTAdd: name = "tv::dla::dwconvt_add<" + t + ">"; break;

@@ -6,7 +6,8 @@
 //   add_relu      relu(a + b): the residual add of a block whose bn2 output is tapped
 //   store_f32     a compute-dtype tensor into the caller's fp32 buffer, exactly (the taps of
 //                 TV_ARCH_RESNET18, which stay in the arena for the next layer's add)
-//   stem7s2_pool  conv1 + bn1 + ReLU + the max-pool from the fp32 NCHW image in one launch (fp16 / bf16)
+//   stem7s2_pool  conv1 + bn1 + ReLU + the max-pool from the fp32 NCHW image, or from u8 NHWC camera frames
+//                 (ToTensor + Normalize through a LUT), in one launch (fp16 / bf16)
 #include <algorithm>
 
 #include "conv_common.h"
@@ -88,9 +89,10 @@ __global__ __launch_bounds__(256) void store_f32(const T* __restrict__ src, floa
 }
 
 // ---- stem7s2_pool: conv1 7x7 / s2 / p3 (3 -> 64) + bn1 + ReLU + MaxPool2d(3, 2, 1) in one launch ----
-// Reads the fp32 NCHW image and writes only the pooled 64-channel tensor: neither the row-expanded
-// staging tensor nor the conv output reaches HBM. A workgroup (4 waves) walks tiles of kTH x kTW
-// pooled pixels on a persistent grid, the folded weights resident in LDS:
+// Reads the fp32 NCHW image (IN = 0) or u8 NHWC frames (IN = 1: ToTensor + ImageNet Normalize through a
+// 768-entry LUT in LDS, yolact_node.py:109-111 at the model size) and writes only the pooled 64-channel
+// tensor: neither the row-expanded staging tensor nor the conv output reaches HBM. A workgroup (4 waves)
+// walks tiles of kTH x kTW pooled pixels on a persistent grid, the folded weights resident in LDS:
 //   1. the tile's input window (kIR x kIC pixels, zero outside the image) -> LDS as T, pixel-major
 //      [row][x * 3 + c]: the 21 values of one kernel row of a conv position are contiguous there;
 //   2. the (2 kTH + 1) x (2 kTW + 1) = 117 conv positions the tile's windows cover as a GEMM on
@@ -110,25 +112,38 @@ constexpr int kIRows = kIR + 1;                        // + one zero row: k-step
 constexpr int kKS = 11, kWS = 184;                     // k-steps of 16; halves per weight row in LDS (176 + 8: 16-byte rows, spread banks)
 constexpr int kCS = 72;                                // halves per conv-tile row in LDS (64 + 8)
 constexpr int kStemLds = (64 * kWS + kIRows * kIRS + 128 * kCS) * 2;
+constexpr int kStemLdsU8 = kStemLds + 768 * 2;         // + the u8 LUT: 48,128 B, three workgroups per CU still fit
+constexpr int kRowDw = 25;  // aligned dwords that cover a staged row's 96 bytes at any byte alignment of its first
+
+__constant__ float kMean[3] = {0.485f, 0.456f, 0.406f};
+__constant__ float kStd[3] = {0.229f, 0.224f, 0.225f};
 
 struct StemPoolArgs {
-  const float* img;      // fp32 NCHW [B, 3, H, W]
+  const void* img;       // IN = 0: fp32 NCHW [B, 3, H, W]; IN = 1: u8 NHWC [B, H, W, 3], any byte alignment
   const void* w;         // T [>= 64][Kpad], K = ky * 24 + kx * 3 + c (zero elsewhere), BatchNorm folded
   const float* bias;     // [64]
   void* out;             // T NHWC [B, PH, PW, 64]
   int B, H, W, CH, CW, PH, PW, Kpad, tiles_y, tiles_x;
 };
 
-template <typename T>
+template <typename T, int IN>
 __global__ __launch_bounds__(256) void stem7s2_pool(StemPoolArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   T* wl = reinterpret_cast<T*>(lds);
   T* il = wl + 64 * kWS;
   T* cl = il + kIRows * kIRS;
+  T* lut = cl + 128 * kCS;  // (IN = 1 only: kStemLdsU8)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int i = tid; i < 64 * (kKS * 2); i += 256) {  // 16-byte chunks of the 64 x 176 weights
     const int n = i / (kKS * 2), c = i % (kKS * 2);
     *reinterpret_cast<uint4*>(wl + n * kWS + c * 8) = *reinterpret_cast<const uint4*>((const T*)p.w + (size_t)n * p.Kpad + c * 8);
+  }
+  if constexpr (IN == 1) {
+    for (int i = tid; i < 768; i += 256) {
+      const int v = i / 3, c = i - v * 3;
+      lut[i] = (T)(((float)v / 255.0f - kMean[c]) / kStd[c]);  // prep_u8's expression, bit for bit
+    }
+    __syncthreads();  // the staging of the first tile reads the LUT
   }
   // this lane's conv position within a tile (positions past the 117th repeat position 0; never pooled)
   const int pos = wave * 32 + (lane & 31), h = lane >> 5;
@@ -140,13 +155,61 @@ __global__ __launch_bounds__(256) void stem7s2_pool(StemPoolArgs p) {
     const int py0 = (tr / p.tiles_x) * kTH, px0 = (tr % p.tiles_x) * kTW;
     const int cy0 = 2 * py0 - 1, cx0 = 2 * px0 - 1;  // first conv position (pool padding 1)
     const int iy0 = 2 * cy0 - 3, ix0 = 2 * cx0 - 3;  // first input pixel (conv padding 3)
-    const float* im = p.img + (size_t)b * 3 * p.H * p.W;
-    for (int i = tid; i < kIRows * kIRS; i += 256) {
-      const int r = i / kIRS, e = i % kIRS, x = e / 3, c = e % 3;
-      const int y = iy0 + r, xx = ix0 + x;
-      float v = 0.f;
-      if (r < kIR && x < kIC && y >= 0 && y < p.H && xx >= 0 && xx < p.W) v = im[((size_t)c * p.H + y) * p.W + xx];
-      il[i] = (T)v;
+#ifdef TV_STEM_U8_BYTES
+    // timing-only variant (make BUILD=build_x LIBDIR=lib_x EXTRA=-DTV_STEM_U8_BYTES): the simplest u8 staging,
+    // one byte load per staged element as the fp32 instance's one value; measured slower (0.37
+    // against 0.27 ms per 32 frames)
+    if constexpr (IN == 1) {
+      const uint8_t* fr = (const uint8_t*)p.img + (size_t)b * p.H * p.W * 3;
+      for (int i = tid; i < kIRows * kIRS; i += 256) {
+        const int r = i / kIRS, e = i % kIRS, x = e / 3, c = e % 3;
+        const int y = iy0 + r, xx = ix0 + x;
+        const bool ok = r < kIR && x < kIC && y >= 0 && y < p.H && xx >= 0 && xx < p.W;
+        il[i] = ok ? lut[(int)fr[((size_t)y * p.W + xx) * 3 + c] * 3 + c] : (T)0;
+      }
+    } else
+#endif
+    if constexpr (IN == 1) {
+      // A window row is the contiguous byte span [(y W + ix0) 3, + 93) of the frame, in the LDS row's own
+      // order. It is read as the aligned dwords that cover it, aligned from the span's own address (the
+      // base may have any byte alignment), one (row, dword) per lane and step, all loads issued before the
+      // first LDS write. Only a dword that holds a byte of the image row is loaded (such a dword lies
+      // inside the allocation); every element outside the image, past column kIC or in the zero row
+      // stages (T)0, not lut[0]: the padding is zero after normalisation.
+      constexpr int NS = (kIRows * kRowDw + 255) / 256;
+      const int elo = 3 * max(0, -ix0), ehi = 3 * min(kIC, p.W - ix0);  // the row's elements inside the image
+      uint32_t raw[NS];
+      int e0[NS];  // the dword's first byte as an element of its row (-3 .. 96)
+      bool ld[NS];
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        const int i = tid + 256 * k, r = i / kRowDw, d = i - r * kRowDw, y = iy0 + r;
+        const bool rok = i < kIRows * kRowDw && r < kIR && y >= 0 && y < p.H;
+        const uint8_t* row = (const uint8_t*)p.img + (((long)b * p.H + (rok ? y : 0)) * p.W + ix0) * 3;
+        e0[k] = 4 * d - (int)((uintptr_t)row & 3);
+        ld[k] = rok && e0[k] + 4 > elo && e0[k] < ehi;  // some byte of the dword is inside the image
+        raw[k] = ld[k] ? *reinterpret_cast<const uint32_t*>(row + e0[k]) : 0u;
+      }
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        const int i = tid + 256 * k, r = i / kRowDw;
+        if (i >= kIRows * kRowDw) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int e = e0[k] + j;
+          if (e < 0 || e >= kIRS) continue;
+          il[r * kIRS + e] = ld[k] && e >= elo && e < ehi ? lut[(int)((raw[k] >> (8 * j)) & 255u) * 3 + e % 3] : (T)0;
+        }
+      }
+    } else {
+      const float* im = (const float*)p.img + (size_t)b * 3 * p.H * p.W;
+      for (int i = tid; i < kIRows * kIRS; i += 256) {
+        const int r = i / kIRS, e = i % kIRS, x = e / 3, c = e % 3;
+        const int y = iy0 + r, xx = ix0 + x;
+        float v = 0.f;
+        if (r < kIR && x < kIC && y >= 0 && y < p.H && xx >= 0 && xx < p.W) v = im[((size_t)c * p.H + y) * p.W + xx];
+        il[i] = (T)v;
+      }
     }
     __syncthreads();  // the window (and, the first time, the weights) staged; the previous tile's pooling done
     f32x16 acc[2] = {};
@@ -284,10 +347,16 @@ int launch_stem7s2_pool(const StemPoolParams& q, int dtype, int cu_count, hipStr
   const long tiles = (long)a.B * a.tiles_y * a.tiles_x;
   // three workgroups per CU fit by LDS (43 KiB each); the tiles of one workgroup amortise its weight load
   const unsigned grid = (unsigned)std::min<long>(tiles, 3L * std::max(1, cu_count));
-  if (dtype == F16)
-    hipLaunchKernelGGL(rn::stem7s2_pool<_Float16>, dim3(grid), dim3(256), rn::kStemLds, s, a);
-  else
-    hipLaunchKernelGGL(rn::stem7s2_pool<__bf16>, dim3(grid), dim3(256), rn::kStemLds, s, a);
+  if (q.u8) {
+    if (dtype == F16)
+      hipLaunchKernelGGL((rn::stem7s2_pool<_Float16, 1>), dim3(grid), dim3(256), rn::kStemLdsU8, s, a);
+    else
+      hipLaunchKernelGGL((rn::stem7s2_pool<__bf16, 1>), dim3(grid), dim3(256), rn::kStemLdsU8, s, a);
+  } else if (dtype == F16) {
+    hipLaunchKernelGGL((rn::stem7s2_pool<_Float16, 0>), dim3(grid), dim3(256), rn::kStemLds, s, a);
+  } else {
+    hipLaunchKernelGGL((rn::stem7s2_pool<__bf16, 0>), dim3(grid), dim3(256), rn::kStemLds, s, a);
+  }
   TV_HIP(hipGetLastError());
   return 0;
 }

@@ -100,6 +100,48 @@ __global__ __launch_bounds__(256) void nms_keys(const float* __restrict__ cls, l
   keys[i] = order_bits(best);
 }
 
+// The node's per-detection outputs (yolact_node.py:129 softmax, :139-141 class / confidence of the kept
+// anchors) for B images: one thread per (image, detection slot). records [B][n_max][8] = anchor, class id
+// (argmax of the logits over all C1 columns, column 0 the background; the lowest index on a tie), its
+// softmax probability, the largest foreground probability (nms_keys' value, the one the NMS ranks by),
+// box y, x, h, w bit for bit; confidence [B][n_max][C1] (or null) the softmax row. Softmax in fp32,
+// max-subtracted, nms_keys' expressions. A slot at or past counts[b] (or whose anchor is outside [0, A))
+// is written as zeros: every row of both outputs is written by every call.
+__global__ __launch_bounds__(128) void detection_records(const float* __restrict__ cls, const float* __restrict__ box,
+                                                         const long long* __restrict__ det,
+                                                         const int* __restrict__ counts, int B, int A, int C1, int n_max,
+                                                         float* __restrict__ records, float* __restrict__ confidence) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (unsigned)B * n_max) return;
+  const unsigned b = i / (unsigned)n_max, d = i % (unsigned)n_max;
+  float4* rec = reinterpret_cast<float4*>(records + (size_t)i * 8);
+  float* conf = confidence ? confidence + (size_t)i * C1 : nullptr;
+  const long long a = (int)d < counts[b] ? det[i] : -1;
+  if (a < 0 || a >= A) {
+    rec[0] = rec[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (conf)
+      for (int j = 0; j < C1; ++j) conf[j] = 0.f;
+    return;
+  }
+  const float* c = cls + ((size_t)b * A + (size_t)a) * C1;
+  float m = c[0];
+  int arg = 0;
+  for (int j = 1; j < C1; ++j) {
+    const float v = c[j];
+    if (v > m) m = v, arg = j;
+  }
+  float s = 0.f;
+  for (int j = 0; j < C1; ++j) s += expf(c[j] - m);
+  float fg = 0.f;
+  for (int j = 0; j < C1; ++j) {
+    const float v = expf(c[j] - m) / s;
+    if (conf) conf[j] = v;
+    if (j) fg = (v > fg || v != v) ? v : fg;
+  }
+  rec[0] = make_float4((float)a, (float)arg, expf(c[arg] - m) / s, fg);
+  rec[1] = reinterpret_cast<const float4*>(box)[(size_t)b * A + (size_t)a];
+}
+
 constexpr int kIouThreads = 256;
 
 // keep[b][j] for the K highest-confidence anchors of image b (sorted order)
@@ -687,6 +729,30 @@ int launch_yolact_assemble_mask(const float* proto, const long long pst[4], int 
   });
   TV_HIP(attr_err);
   hipLaunchKernelGGL(yolact::assemble_mask, grid, dim3(yolact::kMaskThreads), lds, s, p);
+  TV_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_yolact_detection_records(const float* cls, const float* box, const long long* det, const int* counts, int B,
+                                    int A, int C1, int n_max, float* records, float* confidence, hipStream_t s) {
+  if (!cls || !box || !det || !counts || !records) {
+    set_error("detection_records: null pointer");
+    return 1;
+  }
+  if (B < 0 || n_max < 0 || A < 1 || A > (1 << 24) || C1 < 2 || (long long)B * n_max >= (1LL << 31) ||
+      (long long)B * A >= (1LL << 31)) {
+    set_error("detection_records: need 1 <= anchors <= 2^24 (the index is stored as fp32), >= 2 classes (incl. "
+              "background), B * n_max < 2^31");
+    return 1;
+  }
+  if (((uintptr_t)records | (uintptr_t)box) & 15) {
+    set_error("detection_records: records and box must be 16-byte aligned");
+    return 1;
+  }
+  const unsigned n = (unsigned)B * n_max;
+  if (!n) return 0;
+  hipLaunchKernelGGL(yolact::detection_records, dim3((n + 127) / 128), dim3(128), 0, s, cls, box, det, counts, B, A, C1,
+                     n_max, records, confidence);
   TV_HIP(hipGetLastError());
   return 0;
 }

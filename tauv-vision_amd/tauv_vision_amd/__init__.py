@@ -9,7 +9,7 @@ from .dla import DLABackbone  # noqa: F401
 from .decode import (Detection, KeypointDetection, angle_decode, angle_get_bins, decode,  # noqa: F401
                      decode_keypoints, decode_records, depth_decode, heatmap_detect, heatmap_nms)
 from .yolact import (FeaturePyramid, Masknet, PredictionHead, Resnet101Backbone, Yolact, YolactConfig,  # noqa: F401
-                     YolactHead, yolact_head_state_dict)
+                     YolactDetections, YolactDetector, YolactHead, detection_records, yolact_head_state_dict)
 from .localize import DeviceLocalizer, localize_detections, localize_masks  # noqa: F401
 
 __version__ = "0.1.0"

@@ -40,6 +40,11 @@ EXPORTS = {
     "tv_engine_forward_multi": ([c_vp, ctypes.POINTER(c_vp), c_i32, ctypes.POINTER(c_vp), c_i32, c_i32, c_vp], c_i32),
     "tv_engine_profile_multi": ([c_vp, ctypes.POINTER(c_vp), c_i32, ctypes.POINTER(c_vp), c_i32, c_i32, c_vp,
                                  ctypes.POINTER(c_f32), ctypes.POINTER(c_f64), c_i32, ctypes.POINTER(c_i32)], c_i32),
+    "tv_engine_forward_multi_u8": ([c_vp, c_vp, c_i32, ctypes.POINTER(c_vp), c_i32, c_vp], c_i32),
+    "tv_engine_profile_multi_u8": ([c_vp, c_vp, c_i32, ctypes.POINTER(c_vp), c_i32, c_vp, ctypes.POINTER(c_f32),
+                                    ctypes.POINTER(c_f64), c_i32, ctypes.POINTER(c_i32)], c_i32),
+    "tv_engine_op_outputs_multi_u8": ([c_vp, c_vp, c_i32, ctypes.POINTER(c_vp), c_i32, c_vp, ctypes.POINTER(c_vp),
+                                       c_i32], c_i32),
     "tv_diag_bilinear_add": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp], c_i32),
     "tv_engine_create": ([ctypes.POINTER(ModelDesc), ctypes.POINTER(WeightView), c_i32, c_i32,
                           ctypes.POINTER(c_vp)], c_i32),
@@ -87,6 +92,7 @@ EXPORTS = {
                                   c_vp, c_vp], c_i32),
     "tv_yolact_assemble_masks_indexed": ([c_vp, ctypes.POINTER(c_i64), c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32,
                                           c_vp, c_vp, c_i32, c_vp, c_vp], c_i32),
+    "tv_yolact_detection_records": ([c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp], c_i32),
     "tv_localize_boxes": ([c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_f64, c_f64, c_f64, c_f64,
                            c_f64, c_f64, c_f64, c_vp, c_vp], c_i32),
     "tv_localize_masks": ([c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32,

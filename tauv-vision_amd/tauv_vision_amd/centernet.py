@@ -270,11 +270,12 @@ class CenterpointDLA34(_NativeModel):
         return dla34_desc(self.head_channels, in_h, in_w, self.precision)
 
 
-def preprocess(frames: torch.Tensor, in_h: int, in_w: int) -> torch.Tensor:
+def preprocess(frames: torch.Tensor, in_h: int, in_w: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The node's T.ToTensor -> T.Resize((in_h, in_w)) -> T.Normalize(ImageNet)
-    (centernet_node.py:90-92) on the GPU: u8 RGB frames [B, H, W, 3] (or [H, W, 3]) at camera
-    resolution -> normalised fp32 [B, 3, in_h, in_w] (bilinear, align_corners=False, no antialias:
-    torchvision 0.15.2's tensor Resize)."""
+    (centernet_node.py:90-92, yolact_node.py:109-111) on the GPU: u8 RGB frames [B, H, W, 3] (or
+    [H, W, 3]) at camera resolution -> normalised fp32 [B, 3, in_h, in_w] (bilinear,
+    align_corners=False, no antialias: torchvision 0.15.2's tensor Resize). `out`: a caller-owned
+    contiguous fp32 [B, 3, in_h, in_w] buffer on the frames' device (no allocation per call)."""
     if frames.dim() == 3:
         frames = frames.unsqueeze(0)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
@@ -283,7 +284,12 @@ def preprocess(frames: torch.Tensor, in_h: int, in_w: int) -> torch.Tensor:
         raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
     frames = (frames if frames.is_cuda else frames.cuda()).contiguous()
     B, H, W, _ = frames.shape
-    out = torch.empty((B, 3, int(in_h), int(in_w)), dtype=torch.float32, device=frames.device)
+    shape = (B, 3, int(in_h), int(in_w))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=frames.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() \
+            or out.device != frames.device:
+        raise ValueError(f"preprocess: out must be a contiguous fp32 {list(shape)} tensor on {frames.device}")
     if B == 0:
         return out
     _lib.check(_lib.lib().tv_preprocess_u8(ctypes.c_void_p(frames.data_ptr()), B, H, W, int(in_h), int(in_w),

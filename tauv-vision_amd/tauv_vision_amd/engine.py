@@ -110,6 +110,47 @@ class NativeEngine:
                                                       len(outputs), B, _lib.stream_of(self.device)), "forward")
         return outputs
 
+    def forward_multi_u8(self, frames, outputs):
+        """forward_multi from camera frames (yolact_node.py:109-119 at the model size): `frames`
+        contiguous uint8 NHWC RGB [B, in_h, in_w, 3] on this device (any byte alignment: a slice of a
+        larger batch is fine), ToTensor + ImageNet Normalize fused into the first kernel. An arch that
+        takes feature maps raises ValueError before any launch."""
+        B = frames.shape[0]
+        if B == 0:
+            return outputs
+        _lib.check(_lib.lib().tv_engine_forward_multi_u8(self._h, ctypes.c_void_p(frames.data_ptr()), B,
+                                                         self._ptrs(outputs), len(outputs),
+                                                         _lib.stream_of(self.device)), "forward_u8")
+        return outputs
+
+    def profile_multi_u8(self, frames, outputs, cap=4096):
+        """profile_multi() over the buffers of forward_multi_u8."""
+        B = frames.shape[0]
+        ms = (ctypes.c_float * cap)()
+        fl = (ctypes.c_double * cap)()
+        n = ctypes.c_int32()
+        L = _lib.lib()
+        _lib.check(L.tv_engine_profile_multi_u8(self._h, ctypes.c_void_p(frames.data_ptr()), B, self._ptrs(outputs),
+                                                len(outputs), _lib.stream_of(self.device), ms, fl, cap,
+                                                ctypes.byref(n)), "profile")
+        return [(L.tv_engine_op_label(self._h, i).decode(), ms[i], fl[i], L.tv_engine_op_kernel(self._h, B, i).decode())
+                for i in range(min(n.value, cap))]
+
+    def op_outputs_multi_u8(self, frames, outputs):
+        """op_outputs_multi() over the buffers of forward_multi_u8: [(label, kernel, tensor-or-None)] per op."""
+        B = frames.shape[0]
+        shapes = self.op_shapes(B)
+        cdt = {2: torch.float16 if self.desc.compute_dtype == 1 else torch.bfloat16, 4: torch.float32}
+        L = _lib.lib()
+        labels = [L.tv_engine_op_label(self._h, i).decode() for i in range(len(shapes))]
+        bufs = [torch.empty((B, h, w, c), dtype=cdt[eb], device=self.device) if eb else None
+                for (h, w, c, eb) in shapes]
+        dst = (ctypes.c_void_p * len(bufs))(*[None if t is None else t.data_ptr() for t in bufs])
+        _lib.check(L.tv_engine_op_outputs_multi_u8(self._h, ctypes.c_void_p(frames.data_ptr()), B, self._ptrs(outputs),
+                                                   len(outputs), _lib.stream_of(self.device), dst, len(bufs)),
+                   "op_outputs")
+        return [(labels[i], L.tv_engine_op_kernel(self._h, B, i).decode(), bufs[i]) for i in range(len(bufs))]
+
     def profile_multi(self, inputs, outputs, cap=4096):
         """profile() over the buffers of forward_multi."""
         B = inputs[0].shape[0]

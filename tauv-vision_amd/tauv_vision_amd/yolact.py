@@ -10,7 +10,7 @@ exactly like the reference (it is configuration, computed once per FPN level).
 """
 from dataclasses import dataclass
 from math import sqrt
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import ctypes
 import torch
@@ -40,6 +40,13 @@ class YolactConfig:
     n_box_layers: int = 0
     n_mask_layers: int = 0
     n_fpn_downsample_layers: int = 2
+    # the node's T.Normalize (yolact_node.py:111). The kernels hold the ImageNet constants every
+    # reference config uses: forward_frames / detect refuse any other value
+    img_mean: Tuple[float, float, float] = (0.485, 0.456, 0.406)
+    img_stddev: Tuple[float, float, float] = (0.229, 0.224, 0.225)
+
+
+IMAGENET_MEAN, IMAGENET_STDDEV = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
 
 def _head_layers(config):
@@ -130,12 +137,16 @@ def _f32(t, name):
     return _lib.require_gpu_tensor(t, name).contiguous()
 
 
-def _boxes_op(fn, name, a: torch.Tensor, anchor: torch.Tensor, config) -> torch.Tensor:
+def _boxes_op(fn, name, a: torch.Tensor, anchor: torch.Tensor, config, out=None) -> torch.Tensor:
     x = _f32(a, name)
     anc = _f32(anchor, "anchor").to(x.device)
     if x.dim() != 3 or x.shape[-1] != 4 or anc.dim() != 3 or anc.shape[1:] != x.shape[1:]:
         raise ValueError(f"{name}: {tuple(x.shape)} / anchors {tuple(anc.shape)} mismatch")
-    out = torch.empty_like(x)
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(out.shape) != tuple(x.shape) or out.dtype != torch.float32 or not out.is_contiguous() \
+            or out.device != x.device:
+        raise ValueError(f"{name}: out must be a contiguous fp32 {list(x.shape)} tensor on {x.device}")
     B, A, _ = x.shape
     _lib.check(fn(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(anc.data_ptr()), B, A, anc.shape[0],
                   float(config.box_variances[0]), float(config.box_variances[1]), ctypes.c_void_p(out.data_ptr()),
@@ -143,9 +154,10 @@ def _boxes_op(fn, name, a: torch.Tensor, anchor: torch.Tensor, config) -> torch.
     return out
 
 
-def box_decode(box_encoding: torch.Tensor, anchor: torch.Tensor, config) -> torch.Tensor:
-    """boxes.py:55-61 on the GPU: [B, A, 4] encodings + [1 or B, A, 4] anchors -> boxes (y, x, h, w)."""
-    return _boxes_op(_lib.lib().tv_yolact_box_decode, "box_decode", box_encoding, anchor, config)
+def box_decode(box_encoding: torch.Tensor, anchor: torch.Tensor, config, out=None) -> torch.Tensor:
+    """boxes.py:55-61 on the GPU: [B, A, 4] encodings + [1 or B, A, 4] anchors -> boxes (y, x, h, w).
+    `out`: a caller-owned contiguous fp32 [B, A, 4] buffer (no allocation per call)."""
+    return _boxes_op(_lib.lib().tv_yolact_box_decode, "box_decode", box_encoding, anchor, config, out)
 
 
 def box_encode(box: torch.Tensor, anchor: torch.Tensor, config) -> torch.Tensor:
@@ -318,6 +330,56 @@ def assemble_masks_indexed(mask_prototype: torch.Tensor, mask_coeff: torch.Tenso
         A, ctypes.c_void_p(det.data_ptr()), ctypes.c_void_p(counts.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
         _lib.stream_of(proto.device)), "assemble_masks_indexed")
     return out
+
+
+REC = 8  # floats per detection record: anchor, class id, its probability, foreground confidence, y, x, h, w
+
+
+def detection_records(classification: torch.Tensor, box: torch.Tensor, det: torch.Tensor, counts: torch.Tensor,
+                      out: Optional[torch.Tensor] = None, confidence_out: Optional[torch.Tensor] = None):
+    """The node's per-detection outputs (yolact_node.py:129, 139-141) for B images in one launch:
+    classification [B, A, C+1] logits, box [B, A, 4], det [B, n] int64 / counts [B] int32 (BatchedNMS
+    outputs) -> (records [B, n, 8] fp32, confidence). A record is the anchor index, the class id
+    (argmax of the logits over all C+1 columns, column 0 the background, the lowest index on a tie),
+    that class's softmax probability, the largest foreground probability (what nms ranks by) and the
+    box (y, x, h, w) bit for bit. `confidence_out`: a [B, n, C+1] fp32 buffer for the whole softmax
+    rows (the node's confidence_np), returned as the second value (None without it). Every row of
+    both is written by every call; rows at or past counts[b] are zero. `out`: a caller-owned records
+    buffer. No allocation with both buffers given, no host synchronisation."""
+    for t, name, dt in ((classification, "classification", torch.float32), (box, "box", torch.float32),
+                        (det, "det", torch.int64), (counts, "counts", torch.int32)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"detection_records: {name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype != dt:
+            raise ValueError(f"detection_records: {name} must be {dt}, got {t.dtype}")
+    if classification.dim() != 3 or box.dim() != 3 or det.dim() != 2 or counts.dim() != 1:
+        raise ValueError("detection_records: need classification [B, A, C+1], box [B, A, 4], det [B, n], counts [B]")
+    B, A, C1 = classification.shape
+    n = det.shape[1]
+    if tuple(box.shape) != (B, A, 4) or det.shape[0] != B or counts.shape[0] != B:
+        raise ValueError(f"detection_records: classification {list(classification.shape)}, box {list(box.shape)}, "
+                         f"det {list(det.shape)}, counts {list(counts.shape)} do not belong together")
+    if C1 < 2 or A < 1 or A > 1 << 24:
+        raise ValueError("detection_records: need >= 2 classes (with the background) and 1 <= anchors <= 2^24 "
+                         "(the anchor index is stored as fp32)")
+    if not torch.cuda.is_available():
+        raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
+    dev = classification.device
+    for t, name in ((classification, "classification"), (box, "box"), (det, "det"), (counts, "counts")):
+        if not t.is_cuda or t.device != dev:
+            raise ValueError(f"detection_records: {name} is on {t.device}; every tensor must be on one CUDA device")
+        if not t.is_contiguous():
+            raise ValueError(f"detection_records: {name} must be contiguous")
+    out = _check_out(out, (B, n, REC), dev, "detection_records")
+    cptr = None
+    if confidence_out is not None:
+        confidence_out = _check_out(confidence_out, (B, n, C1), dev, "detection_records confidence")
+        cptr = ctypes.c_void_p(confidence_out.data_ptr())
+    _lib.check(_lib.lib().tv_yolact_detection_records(
+        ctypes.c_void_p(classification.data_ptr()), ctypes.c_void_p(box.data_ptr()), ctypes.c_void_p(det.data_ptr()),
+        ctypes.c_void_p(counts.data_ptr()), B, A, C1, n, ctypes.c_void_p(out.data_ptr()), cptr,
+        _lib.stream_of(dev)), "detection_records")
+    return out, confidence_out
 
 
 # ---- the neck and the head: everything of Yolact.forward after the backbone (model.py:34-60) ----
@@ -534,6 +596,45 @@ def _image(img):
     return img.to(torch.float32).contiguous()
 
 
+def _check_normalisation(config):
+    """The kernels normalise with the ImageNet constants: refuse a config that asks for others."""
+    if config is None:
+        return
+    mean = tuple(float(v) for v in getattr(config, "img_mean", IMAGENET_MEAN))
+    std = tuple(float(v) for v in getattr(config, "img_stddev", IMAGENET_STDDEV))
+    if mean != IMAGENET_MEAN or std != IMAGENET_STDDEV:
+        raise ValueError(f"img_mean {mean} / img_stddev {std}: the frame kernels normalise with the ImageNet values "
+                         f"{IMAGENET_MEAN} / {IMAGENET_STDDEV} only; normalise yourself and call forward(img)")
+
+
+def _frames(frames, size, config):
+    """Camera frames as uint8 [B, H, W, 3] and the model's (in_h, in_w) (`size`, or the frames' own):
+    Centernet.forward_frames' argument checks, every one of them before the GPU is needed."""
+    if not isinstance(frames, torch.Tensor):
+        raise ValueError(f"frames must be a torch tensor, got {type(frames).__name__}")
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(0)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError(f"frames must be uint8 [B, H, W, 3], got {frames.dtype} {list(frames.shape)}")
+    if frames.shape[1] < 1 or frames.shape[2] < 1:
+        raise ValueError(f"frames must be uint8 [B, H, W, 3] with H, W >= 1, got {list(frames.shape)}")
+    if size is None:
+        in_h, in_w = frames.shape[1], frames.shape[2]
+    else:
+        if len(size) != 2 or int(size[0]) < 1 or int(size[1]) < 1:
+            raise ValueError(f"size must be (in_h, in_w), got {size}")
+        in_h, in_w = int(size[0]), int(size[1])
+    _check_normalisation(config)
+    return frames, (in_h, in_w)
+
+
+def _frames_on_gpu(frames):
+    """The frames, contiguous, on their CUDA device (the current one for host frames)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
+    return (frames if frames.is_cuda else frames.cuda()).contiguous()
+
+
 class Resnet101Backbone(_NativeNet):
     """yolact/model/backbone.py:9-32 (the reference's class name; the network is torchvision's
     resnet18): img [B, 3, H, W] -> (c3, c4, c5), the outputs of layer2.1.bn2, layer3.1.bn2 and
@@ -573,17 +674,36 @@ class Resnet101Backbone(_NativeNet):
         n = len("_feature_extractor.")
         return {k[n:]: v for k, v in self.state_dict().items()}
 
-    def forward_nhwc(self, img, out=None):
-        x = _image(img)
-        B, _, H, W = x.shape
-        dev = x.device
+    def _run(self, x, H, W, out, u8):
+        B, dev = x.shape[0], x.device
         eng = self._engine((dev.index, (H, W)), lambda: resnet18_desc(H, W, self.precision), self.backbone_state_dict)
         outs = _outputs(out, [(B, h, w, cp) for h, w, _, cp in model_io(eng.desc)[1]], dev, "Resnet101Backbone")
-        eng.forward_multi([x], outs)
+        if u8:
+            eng.forward_multi_u8(x, outs)
+        else:
+            eng.forward_multi([x], outs)
         return tuple(outs)
+
+    def forward_nhwc(self, img, out=None):
+        x = _image(img)
+        return self._run(x, x.shape[2], x.shape[3], out, False)
 
     def forward(self, img, out=None):
         return tuple(o.permute(0, 3, 1, 2) for o in self.forward_nhwc(img, out))
+
+    def forward_frames(self, frames, size=None, out=None):
+        """Raw uint8 RGB camera frames [B, H, W, 3] (or [H, W, 3]) through the node's preprocessing
+        (yolact_node.py:109-111: ToTensor -> Resize(size) -> Normalize) and forward: exactly what
+        forward returns. size = (in_h, in_w) of the model (None: the frames' own size). At the model
+        size the frames go straight to the native plan (ToTensor + Normalize in the stem kernel's LUT;
+        in fp32 in the staging kernel); otherwise `preprocess` resizes + normalises into the fp32
+        forward() input first."""
+        from .centernet import preprocess
+        frames, (in_h, in_w) = _frames(frames, size, self.config)
+        frames = _frames_on_gpu(frames)
+        if (in_h, in_w) != (frames.shape[1], frames.shape[2]):
+            return self.forward(preprocess(frames, in_h, in_w), out)
+        return tuple(o.permute(0, 3, 1, 2) for o in self._run(frames, in_h, in_w, out, True))
 
 
 class Yolact(YolactHead):
@@ -626,18 +746,208 @@ class Yolact(YolactHead):
         if not self._native():
             return super().forward(self._backbone(img), out)
         x = _image(img)
-        B, _, H, W = x.shape
+        return self._run(x, x.shape[2], x.shape[3], out, False)
+
+    def _image_engine(self, dev, H, W):
+        """The one-plan engine of an H x W image on `dev` and its FPN level sizes."""
         levels = self.level_sizes(Resnet101Backbone.map_sizes(H, W))
         if len(levels) > len(self.config.anchor_scales):
             raise ValueError(f"{len(levels)} FPN levels but {len(self.config.anchor_scales)} anchor_scales")
-        dev = x.device
         c = self.config
         eng = self._engine((dev.index, ("img", H, W)),
                            lambda: yolact_desc(H, W, int(c.feature_depth), int(c.n_fpn_downsample_layers),
                                                int(c.n_classes), int(c.n_prototype_masks),
                                                len(c.anchor_aspect_ratios), _head_layers(c), self.precision),
                            self.state_dict)
+        return eng, levels
+
+    def output_shapes(self, B, H, W, device):
+        """The shapes of the four `out` buffers (classification, box_encoding, mask_coeff, mask_prototype
+        NHWC) of a B-frame forward of H x W images on the native backbone."""
+        eng, _ = self._image_engine(device, H, W)
         (A, _, c1, _), _, (_, _, k, _), (ph, pw, _, kp) = model_io(eng.desc)[1]
-        outs = _outputs(out, [(B, A, c1), (B, A, 4), (B, A, k), (B, ph, pw, kp)], dev, "Yolact")
-        eng.forward_multi([x], outs)
+        return [(B, A, c1), (B, A, 4), (B, A, k), (B, ph, pw, kp)]
+
+    def _run(self, x, H, W, out, u8):
+        B, dev = x.shape[0], x.device
+        eng, levels = self._image_engine(dev, H, W)
+        k = model_io(eng.desc)[1][2][2]
+        outs = _outputs(out, self.output_shapes(B, H, W, dev), dev, "Yolact")
+        if u8:
+            eng.forward_multi_u8(x, outs)
+        else:
+            eng.forward_multi([x], outs)
         return outs[0], outs[1], outs[2], self.anchor(levels, dev), outs[3][..., :k].permute(0, 3, 1, 2)
+
+    def forward_frames(self, frames, size=None, out=None):
+        """Raw uint8 RGB camera frames [B, H, W, 3] (or [H, W, 3]) through the node's preprocessing
+        (yolact_node.py:109-111: ToTensor -> Resize(size) -> Normalize) and forward (:119): exactly what
+        forward returns. size = (in_h, in_w) of the model (None: the frames' own size). With the native
+        backbone and frames at the model size, ToTensor + Normalize run inside the plan's first kernel
+        and the fp32 image never exists; otherwise `preprocess` resizes + normalises into the fp32
+        forward() input first."""
+        from .centernet import preprocess
+        frames, (in_h, in_w) = _frames(frames, size, self.config)
+        if getattr(self, "_backbone", None) is None:
+            return self.forward(None)  # (raises: no backbone)
+        frames = _frames_on_gpu(frames)
+        if not self._native() or (in_h, in_w) != (frames.shape[1], frames.shape[2]):
+            return self.forward(preprocess(frames, in_h, in_w), out)
+        return self._run(frames, in_h, in_w, out, True)
+
+    def invalidate(self):
+        super().invalidate()
+        self._detectors = {}
+
+    def detect(self, frames, top_k, iou_threshold, confidence_threshold, depth=None, camera=None):
+        """The node's callback from the camera frame to the detections (yolact_node.py:109-143) in one
+        call: uint8 RGB frames [B, H, W, 3] (or [H, W, 3]) of any size, resized to (config.in_h,
+        config.in_w), through a cached YolactDetector (native backbone). depth (uint16 millimetres,
+        [dh, dw] or [B, dh, dw], numpy or torch) with camera = (fx, fy, cx, cy) also localises every
+        detection (:177-193). Returns YolactDetections(records [B, K, 8] and counts [B] on the host,
+        the masks [B, K, 4h, 4w] on the device — the detector's static buffer, overwritten by the next
+        call —, points [B, K, 8] on the host or None); K = min(top_k, anchors). One device-to-host
+        synchronisation."""
+        from .localize import _host_depth
+        frames, _ = _frames(frames, None, self.config)
+        if int(top_k) < 1:
+            raise ValueError(f"top_k must be >= 1, got {top_k}")
+        if (depth is None) != (camera is None):
+            raise ValueError("depth and camera = (fx, fy, cx, cy) go together")
+        if camera is not None and len(camera) != 4:
+            raise ValueError(f"camera must be (fx, fy, cx, cy), got {camera}")
+        if not self._native():
+            raise ValueError("detect needs the native backbone: Yolact(config, backbone=Resnet101Backbone(config))")
+        B = frames.shape[0]
+        if depth is not None:
+            depth = _host_depth(depth, max(B, 1))
+        frames = _frames_on_gpu(frames)
+        dev = frames.device
+        hw, size = (frames.shape[1], frames.shape[2]), (int(self.config.in_h), int(self.config.in_w))
+        key = (dev.index, B, hw, size, int(top_k), self.precision, self._version_key())
+        det = getattr(self, "_detectors", {}).get(key)
+        if det is None:
+            det = YolactDetector(self, B, hw, int(top_k), dev, size)
+            self._detectors = {key: det}
+        res = det(frames, iou_threshold, confidence_threshold, None if depth is None else depth.to(dev), camera)
+        records, counts, points = det.host()
+        return YolactDetections(records.clone(), counts.clone(), res.masks, None if points is None else points.clone())
+
+
+class YolactDetections(NamedTuple):
+    """records [B, K, 8] fp32 (anchor, class id, its probability, foreground confidence, y, x, h, w;
+    rows at or past counts[b] zero), counts [B] int32, masks [B, K, 4h, 4w] fp32 on the device (rows
+    past counts[b] are not written), points [B, K, 8] fp32 (DeviceLocalizer's x, y, z, valid, n_pixels,
+    depth_sum, e_x, e_y) or None without depth."""
+    records: torch.Tensor
+    counts: torch.Tensor
+    masks: torch.Tensor
+    points: Optional[torch.Tensor]
+
+
+class YolactDetector:
+    """The node's callback from the camera frames to the detections (yolact_node.py:109-143) for one
+    (B, frame size) with static device buffers: forward_frames(out=...) -> box_decode -> BatchedNMS ->
+    assemble_masks_indexed -> detection_records and, with depth, DeviceLocalizer.masks(bound_by_box).
+    `model`: a Yolact on the native backbone; frame_hw = (H, W) of the camera frames; size = (in_h,
+    in_w) of the model (None: the frames' own size; another size runs `preprocess` into a static fp32
+    image first); K = min(top_k, anchors).
+
+    A call launches on the current stream, allocates nothing and never synchronises, so it can be
+    captured in a graph after one eager call on the capture stream (the pattern of YolactHead(out=...)).
+    The buffers — `head_out` (classification, box_encoding, mask_coeff, mask_prototype NHWC), `box`
+    [B, A, 4], `det` [B, K] int64, `masks` [B, K, 4h, 4w], `points` [B, K, 8], and `records` [B, K, 8] +
+    `counts` [B] as views of one allocation `packed` (DeviceDecoder's layout: one copy carries both) —
+    are overwritten by every call. Mask rows past counts[b] are not written (they start as zeros)."""
+
+    def __init__(self, model, B, frame_hw, top_k, device, size=None):
+        from .localize import DeviceLocalizer
+        if not isinstance(model, Yolact) or not model._native():
+            raise ValueError("YolactDetector needs a Yolact on the native backbone "
+                             "(Yolact(config, backbone=Resnet101Backbone(config)))")
+        if int(B) < 1 or int(top_k) < 1 or len(frame_hw) != 2 or min(int(v) for v in frame_hw) < 1:
+            raise ValueError(f"YolactDetector needs B >= 1, top_k >= 1 and frame_hw = (H, W), got {B}, {top_k}, {frame_hw}")
+        _check_normalisation(model.config)
+        self.model, self.B, self.top_k = model, int(B), int(top_k)
+        self.frame_hw = (int(frame_hw[0]), int(frame_hw[1]))
+        self.size = self.frame_hw if size is None else (int(size[0]), int(size[1]))
+        if not torch.cuda.is_available():
+            raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"YolactDetector needs a GPU device, got {self.device}")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        dev = self.device
+        shapes = model.output_shapes(self.B, self.size[0], self.size[1], dev)
+        self.head_out = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
+        (_, A, _), _, _, (_, ph, pw, _) = shapes
+        self.img = None if self.size == self.frame_hw else \
+            torch.empty((self.B, 3) + self.size, dtype=torch.float32, device=dev)
+        self.box = torch.empty((self.B, A, 4), dtype=torch.float32, device=dev)
+        self.nms = BatchedNMS(self.B, A, self.top_k, dev)
+        self.K = K = self.nms.K
+        nrec = self.B * K * REC
+        self.packed = torch.zeros((nrec + self.B) * 4, dtype=torch.uint8, device=dev)
+        self.records = self.packed[:nrec * 4].view(torch.float32).view(self.B, K, REC)
+        self.counts = self.nms.counts = self.packed[nrec * 4:].view(torch.int32)  # (the NMS writes them here)
+        self.det = self.nms.det
+        self.masks = torch.zeros((self.B, K, ph, pw), dtype=torch.float32, device=dev)
+        self.localizer = DeviceLocalizer(self.B, K, dev)
+        self.points = self.localizer.out
+        self._localized = False
+        self._host = None
+
+    def __call__(self, frames, iou_threshold, confidence_threshold, depth=None, camera=None):
+        """frames: uint8 [B, H, W, 3] of the detector's frame size on its device — or the normalised
+        fp32 image [B, 3, in_h, in_w] (the fp32 entry, for frames preprocessed elsewhere). depth: uint16
+        millimetres [1 or B, dh, dw] on the device, with camera = (fx, fy, cx, cy). Returns
+        YolactDetections of the static device buffers (points None without depth)."""
+        from .centernet import preprocess
+        m = self.model
+        if (depth is None) != (camera is None):
+            raise ValueError("depth and camera = (fx, fy, cx, cy) go together")
+        if camera is not None and len(camera) != 4:
+            raise ValueError(f"camera must be (fx, fy, cx, cy), got {camera}")
+        if not isinstance(frames, torch.Tensor) or frames.device != self.device:
+            raise ValueError(f"frames must be a tensor on {self.device}")
+        if frames.dtype == torch.float32:
+            if tuple(frames.shape) != (self.B, 3) + self.size:
+                raise ValueError(f"the fp32 image must be {[self.B, 3, *self.size]}, got {list(frames.shape)}")
+            pred = m.forward(frames, out=self.head_out)
+        else:
+            frames, _ = _frames(frames, None, m.config)
+            if tuple(frames.shape) != (self.B,) + self.frame_hw + (3,):
+                raise ValueError(f"YolactDetector built for frames {[self.B, *self.frame_hw, 3]}, got {list(frames.shape)}")
+            if self.img is None:
+                pred = m.forward_frames(frames, out=self.head_out)
+            else:
+                pred = m.forward(preprocess(frames, self.size[0], self.size[1], out=self.img), out=self.head_out)
+        classification, box_encoding, mask_coeff, anchor, mask_prototype = pred
+        box = box_decode(box_encoding, anchor, m.config, out=self.box)
+        det, counts = self.nms(classification, box, iou_threshold, confidence_threshold)
+        assemble_masks_indexed(mask_prototype, mask_coeff, box, det, counts, out=self.masks)
+        detection_records(classification, box, det, counts, out=self.records)
+        self._localized = depth is not None
+        if self._localized:
+            fx, fy, cx, cy = camera
+            self.localizer.masks(self.masks, counts, det, box, depth, fx, fy, cx, cy, bound_by_box=True)
+        return YolactDetections(self.records, self.counts, self.masks, self.points if self._localized else None)
+
+    def host(self):
+        """(records [B, K, 8], counts [B], points [B, K, 8] or None) of the last call on the host: the
+        packed records (and the points) copied to pinned memory, one synchronisation. The tensors are
+        views of the detector's pinned mirror, overwritten by the next host()."""
+        nrec = self.B * self.K * REC * 4
+        if self._host is None:
+            self._host = torch.empty(self.packed.numel() + nrec, dtype=torch.uint8, pin_memory=True)
+        h = self._host
+        with torch.cuda.device(self.device):
+            h[:self.packed.numel()].copy_(self.packed, non_blocking=True)
+            if self._localized:
+                h[self.packed.numel():].copy_(self.points.view(-1).view(torch.uint8), non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+        rec = h[:nrec].view(torch.float32).view(self.B, self.K, REC)
+        cnt = h[nrec:self.packed.numel()].view(torch.int32)
+        pts = h[self.packed.numel():].view(torch.float32).view(self.B, self.K, REC) if self._localized else None
+        return rec, cnt, pts

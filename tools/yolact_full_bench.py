@@ -10,17 +10,23 @@ trunk block, two extra levels), batch 32 and batch 1:
             the weights and the image cast to the same dtype;
   knob A/B  the fused plan built through tv_engine_create_diag with each of --knobs (e.g. TV_RSTEM=0)
             against the default, alternating on the same box; a knob the library does not know is
-            reported as such.
+            reported as such;
+  frames    Yolact.forward_frames on uint8 NHWC camera frames at the model size (ToTensor + Normalize in
+            the stem kernel's LUT), caller-owned outputs, as a replayed graph;
+  torch_prep_then_fused  what a caller did before forward_frames existed: the torch-op ToTensor +
+            Normalize of the same u8 frames into the fp32 NCHW image (eager), then the `fused` graph.
 
 Each is timed with device events around `--steps` iterations after `--warmup` (a synchronise ends each
 window), `--repeats` times, the variants alternating, on seeded inputs resident on the device: min /
 median / max over the repeats. In separate passes: the per-op profile of the fused step (one op per
 launch) summed per part — stem + pool, layer1..4, FPN, protonet, heads — against the same part in
-PyTorch, so that a native part slower than its PyTorch counterpart is named (`slower_than_torch`).
+PyTorch, so that a native part slower than its PyTorch counterpart is named (`slower_than_torch`), and the
+stem + pool row of the same profile over the u8 frames next to the fp32 one (`stem_pool_ms`).
 Prints one JSON line per batch and writes everything to --out.
 
 Usage: python tools/yolact_full_bench.py [--batches 32,1] [--precision fp16] [--steps 100] [--warmup 10]
                                          [--repeats 3] [--knobs TV_RSTEM=0] [--out profiles/yolact_full/bench.json]
+                                         [--lib tauv-vision_amd/lib_x/libtauv_vision_amd.so]
 """
 import argparse
 import json
@@ -56,20 +62,22 @@ def spread(v):
     return {"min": round(min(v), 4), "median": round(statistics.median(v), 4), "max": round(max(v), 4)}
 
 
-def graphed(net, img, dev):
-    """One eager step on the capture stream (workspaces, anchors), then the captured `out=` step."""
+def graphed(net, img, dev, fwd=None):
+    """One eager step on the capture stream (workspaces, anchors), then the captured `out=` step. `fwd`:
+    the entry (net.forward_frames for uint8 frames; default the fp32 forward)."""
+    fwd = fwd or net
     s = torch.cuda.Stream(dev)
     s.wait_stream(torch.cuda.current_stream(dev))
     with torch.cuda.stream(s):
-        first = net(img)
+        first = fwd(img)
         out = [torch.empty_like(first[0]), torch.empty_like(first[1]), torch.empty_like(first[2]),
                torch.empty((img.shape[0],) + tuple(first[4].shape[2:]) + ((first[4].shape[1] + 3) // 4 * 4,), device=dev)]
-        net(img, out=out)
+        fwd(img, out=out)
         s.synchronize()
     torch.cuda.current_stream(dev).wait_stream(s)
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph, stream=s):
-        net(img, out=out)
+        fwd(img, out=out)
     return graph, out
 
 
@@ -95,6 +103,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--knobs", default="TV_RSTEM=0")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "yolact_full", "bench.json"))
+    ap.add_argument("--lib", default="", help="another build of the library (an experiment build: make BUILD=... LIBDIR=... EXTRA=...)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("yolact_full_bench needs the MI355X: no HIP device is visible")
@@ -102,8 +111,10 @@ def main():
     import resnet18_ref as rr
     import yolact_head_ref as yr
     from recipe_yolact_head import SCALES, VAR, head_case, head_inputs
-    from tauv_vision_amd import engine as tv_engine
+    from tauv_vision_amd import _lib, engine as tv_engine
     from tauv_vision_amd.weights import geometry
+    if a.lib:
+        _lib.set_library_path(os.path.abspath(a.lib))
     from tauv_vision_amd.yolact import Resnet101Backbone, Yolact, YolactConfig, YolactHead
 
     c = head_case("yolact_head_d")
@@ -145,7 +156,26 @@ def main():
             with torch.no_grad():
                 return yr.yolact_head(hsd, list(ref(imgd)), c["C"], c["k"])
 
-        variants = {"fused_graph_ms": graph.replay, "two_call_eager_ms": two_call, "torch_eager_ms": torch_step}
+        # from the camera's bytes: the u8 entry as a replayed graph, and the torch-op normalisation of the same
+        # frames into a resident fp32 image followed by the fused graph over that image
+        frames = torch.randint(0, 256, (B, c["in_h"], c["in_w"], 3), generator=torch.Generator(device=dev).manual_seed(2201),
+                               dtype=torch.uint8, device=dev)
+        fgraph, fout = graphed(net, frames, dev, net.forward_frames)
+        mean = torch.tensor(cfg.img_mean, device=dev).view(1, 3, 1, 1)
+        std = torch.tensor(cfg.img_stddev, device=dev).view(1, 3, 1, 1)
+        pimg = torch.empty_like(img)
+        pgraph, pout = graphed(net, pimg, dev)
+
+        def prep_then_fused():
+            pimg.copy_((frames.permute(0, 3, 1, 2).float() / 255.0 - mean) / std)
+            pgraph.replay()
+
+        prep_then_fused()
+        fgraph.replay()
+        torch.cuda.synchronize()
+        frames_equal = all(bool(torch.equal(x, y)) for x, y in zip(fout, pout))
+        variants = {"fused_graph_ms": graph.replay, "two_call_eager_ms": two_call, "torch_eager_ms": torch_step,
+                    "frames_graph_ms": fgraph.replay, "torch_prep_then_fused_graph_ms": prep_then_fused}
         # the knob A/B: the same plan built with each override, as replayed graphs on this box
         knob_note = {}
         for kv in [k for k in a.knobs.split(",") if k]:
@@ -176,6 +206,14 @@ def main():
         native = {}
         for r in rows:
             native[part_of(r[0])] = native.get(part_of(r[0]), 0.0) + r[1]
+        # the stem alone from either input kind: the stem + pool rows of alternating one-op-per-launch profiles
+        stem = {"fp32": [], "u8": []}
+        for _ in range(5):
+            for kind, prof in (("fp32", lambda: eng.profile_multi([img], out)), ("u8", lambda: eng.profile_multi_u8(frames, fout))):
+                stem[kind].append(sum(r[1] for r in prof() if part_of(r[0]) == "stem + pool"))
+        u8_rows = eng.profile_multi_u8(frames, fout)
+        stem_kernel = {"fp32": [r[3] for r in rows if r[0].startswith(BB + "maxpool")],
+                       "u8": [r[3] for r in u8_rows if r[0].startswith(BB + "maxpool")]}
         psteps, pwarm = max(10, a.steps // 3), 3
         with torch.no_grad():
             x0 = ref.maxpool(F.relu(ref.bn1(ref.conv1(imgd))))
@@ -215,12 +253,17 @@ def main():
                "gflop_per_frame": round(flops / 1e9, 3), "native_tflops": round(flops * B / ng / 1e9, 2),
                "slices": eng.slices(B), "knobs": knob_note, "rel_diff_native_vs_torch": err, "steps": a.steps,
                "warmup": a.warmup, "repeats": a.repeats, "slower_than_torch": slower,
-               "device": torch.cuda.get_device_name(0)}
+               "frames_over_fused_graph": round(statistics.median(runs["frames_graph_ms"]) / ng, 4),
+               "frames_graph_no_slower_than_fused_graph": statistics.median(runs["frames_graph_ms"]) <= ng,
+               "frames_outputs_equal_torch_prep_outputs": frames_equal,
+               "stem_pool_ms": {k: spread(v) for k, v in stem.items()}, "stem_pool_kernel": stem_kernel,
+               "stem_u8_no_slower_than_fp32": statistics.median(stem["u8"]) <= statistics.median(stem["fp32"]),
+               "library": a.lib or "default", "device": torch.cuda.get_device_name(0)}
         print(json.dumps(res), flush=True)
         res["parts"] = breakdown
         res["ops"] = [{"label": r[0], "ms": round(r[1], 4), "gflop": round(r[2] / 1e9, 4), "kernel": r[3]} for r in rows]
         results.append(res)
-        del net, graph, head
+        del net, graph, head, fgraph, pgraph
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(results, f, indent=1)
