@@ -174,10 +174,35 @@ def stream_of(device):
     return c_vp(torch.cuda.current_stream(device).cuda_stream)
 
 
-def require_gpu_tensor(t, name):
+def require_gpu():
     import torch
     if not torch.cuda.is_available():
         raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
+
+
+def current_cuda(t):
+    """`t`'s device if it is on a GPU, else the current GPU; raises without one."""
+    import torch
+    require_gpu()
+    return t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+
+
+def check_out(out, shape, device, what):
+    """A caller-owned output buffer, which a kernel writes through its raw pointer: a contiguous
+    fp32 tensor of exactly `shape` on `device` (None: a fresh one)."""
+    import torch
+    if out is None:
+        return torch.empty(tuple(shape), dtype=torch.float32, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous() \
+            or out.device != device:
+        raise ValueError(f"{what}: out must be a contiguous fp32 {list(shape)} tensor on {device}, got "
+                         f"{out.dtype} {list(out.shape)} on {out.device}")
+    return out
+
+
+def require_gpu_tensor(t, name):
+    import torch
+    require_gpu()
     if not t.is_cuda:
         t = t.cuda()
     if t.dtype != torch.float32:

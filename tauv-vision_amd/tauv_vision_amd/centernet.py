@@ -19,6 +19,7 @@ from . import _lib
 from .config import ObjectConfigSet
 from .dla import DLABackbone, populate
 from .engine import NativeEngine
+from .native import NativeModule
 from .weights import model_desc, dla34_desc, param_layout
 
 _GRAPH_LOCK = threading.RLock()  # the forward graph cache's launches and captures (all models)
@@ -87,61 +88,29 @@ def prediction_from_nhwc(out: torch.Tensor, object_config: ObjectConfigSet) -> P
     return Prediction(**fields)
 
 
-class _NativeModel(nn.Module):
-    """Engine cache + the reference forward API shared by Centernet and CenterpointDLA34.
-    Subclasses provide `_desc(in_h, in_w)` (the native model description) and `_key()`."""
+class _NativeModel(NativeModule):
+    """The reference forward API shared by Centernet and CenterpointDLA34, behind a cache of captured
+    forward graphs. Subclasses provide `_desc(in_h, in_w)` (the native model description)."""
 
     def _init_native(self, object_config, precision):
+        super()._init_native(precision)
         self.object_config = object_config
         self.head_channels = get_head_channels(object_config)
-        if precision not in _lib.DTYPES:
-            raise ValueError(f"precision must be one of {sorted(_lib.DTYPES)}")
-        self.precision = precision
-        self._version = [0]
-        self._engines = {}
         # hipGraph replay behind forward()/forward_frames(): a (kind, shape) seen before is replayed
         # from a captured graph instead of launched op by op (set False for eager launches only)
         self.graph_replay = True
         self._graphs = {}
-        self.register_load_state_dict_post_hook(lambda module, keys: module.invalidate())
 
-    # -- engine cache ---------------------------------------------------------------
     def invalidate(self):
-        self._version[0] += 1
-        self._engines = {}
+        super().invalidate()
         self._graphs = {}
 
-    def _apply(self, fn, *args, **kwargs):
-        r = super()._apply(fn, *args, **kwargs)
-        self.invalidate()
-        return r
-
-    def set_precision(self, precision: str):
-        if precision not in _lib.DTYPES:
-            raise ValueError(f"precision must be one of {sorted(_lib.DTYPES)}")
-        self.precision = precision
-        self.invalidate()
-        return self
-
-    def _key(self):
-        return (self._version[0],)
-
     def _device_for(self, t: torch.Tensor) -> torch.device:
-        if not torch.cuda.is_available():
-            raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
-        if t.is_cuda:
-            return t.device
-        p = next(self.parameters())
-        return p.device if p.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        """`t`'s GPU; a host tensor goes to the parameters' GPU (the current one if they are on the host)."""
+        return _lib.current_cuda(t if t.is_cuda else next(self.parameters()))
 
     def engine(self, device: torch.device, in_h: int, in_w: int) -> NativeEngine:
-        key = (device.index if device.index is not None else torch.cuda.current_device(), in_h, in_w,
-               self.precision) + self._key()
-        eng = self._engines.get(key)
-        if eng is None:
-            eng = NativeEngine(self._desc(in_h, in_w), self.state_dict(), key[0])
-            self._engines = {key: eng}
-        return eng
+        return self._engine(device, (in_h, in_w), lambda: self._desc(in_h, in_w), self.state_dict)
 
     # -- graph cache ------------------------------------------------------------------
     def _launch(self, eng: NativeEngine, kind: str, x: torch.Tensor) -> torch.Tensor:
@@ -243,9 +212,6 @@ class Centernet(_NativeModel):
         self.heads = nn.Module()
         populate(self.heads, [(k[len("heads."):], s) for k, s in layout], seed_layout=layout, prefix="heads.")
 
-    def _key(self):
-        return (self._version[0], self.backbone._version[0])
-
     def _desc(self, in_h, in_w):
         return model_desc(self.backbone.heights, self.backbone.channels, self.backbone.downsamples,
                           self.head_channels, in_h, in_w, self.precision)
@@ -280,16 +246,10 @@ def preprocess(frames: torch.Tensor, in_h: int, in_w: int, out: Optional[torch.T
         frames = frames.unsqueeze(0)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
         raise ValueError("frames must be uint8 [B, H, W, 3]")
-    if not torch.cuda.is_available():
-        raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
+    _lib.require_gpu()
     frames = (frames if frames.is_cuda else frames.cuda()).contiguous()
     B, H, W, _ = frames.shape
-    shape = (B, 3, int(in_h), int(in_w))
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=frames.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() \
-            or out.device != frames.device:
-        raise ValueError(f"preprocess: out must be a contiguous fp32 {list(shape)} tensor on {frames.device}")
+    out = _lib.check_out(out, (B, 3, int(in_h), int(in_w)), frames.device, "preprocess")
     if B == 0:
         return out
     _lib.check(_lib.lib().tv_preprocess_u8(ctypes.c_void_p(frames.data_ptr()), B, H, W, int(in_h), int(in_w),
@@ -313,5 +273,5 @@ def initialize_weights(module: nn.Module, excluded_modules=()):
                 if b is not None:
                     b.zero_()
     for m in module.modules():
-        if isinstance(m, _NativeModel):
+        if isinstance(m, NativeModule):
             m.invalidate()

@@ -123,45 +123,48 @@ class NativeEngine:
                                                          _lib.stream_of(self.device)), "forward_u8")
         return outputs
 
-    def profile_multi_u8(self, frames, outputs, cap=4096):
-        """profile_multi() over the buffers of forward_multi_u8."""
-        B = frames.shape[0]
+    def _profile_rows(self, B, call, cap):
+        """[(label, ms, flops, kernel)] per launch of the profiled forward `call(L, ms, fl, cap, n)` makes."""
         ms = (ctypes.c_float * cap)()
         fl = (ctypes.c_double * cap)()
         n = ctypes.c_int32()
         L = _lib.lib()
-        _lib.check(L.tv_engine_profile_multi_u8(self._h, ctypes.c_void_p(frames.data_ptr()), B, self._ptrs(outputs),
-                                                len(outputs), _lib.stream_of(self.device), ms, fl, cap,
-                                                ctypes.byref(n)), "profile")
+        _lib.check(call(L, ms, fl, cap, ctypes.byref(n)), "profile")
         return [(L.tv_engine_op_label(self._h, i).decode(), ms[i], fl[i], L.tv_engine_op_kernel(self._h, B, i).decode())
                 for i in range(min(n.value, cap))]
 
-    def op_outputs_multi_u8(self, frames, outputs):
-        """op_outputs_multi() over the buffers of forward_multi_u8: [(label, kernel, tensor-or-None)] per op."""
-        B = frames.shape[0]
+    def _tap(self, B, call):
+        """[(label, kernel, tensor-or-None)] per op of the one-op-per-launch forward `call(L, dst, n)`
+        makes: the tensor NHWC [B, H, W, C] in the compute dtype (fp32 for fp32 tensors), None for an op
+        that stores nothing of its own."""
         shapes = self.op_shapes(B)
         cdt = {2: torch.float16 if self.desc.compute_dtype == 1 else torch.bfloat16, 4: torch.float32}
         L = _lib.lib()
-        labels = [L.tv_engine_op_label(self._h, i).decode() for i in range(len(shapes))]
         bufs = [torch.empty((B, h, w, c), dtype=cdt[eb], device=self.device) if eb else None
                 for (h, w, c, eb) in shapes]
         dst = (ctypes.c_void_p * len(bufs))(*[None if t is None else t.data_ptr() for t in bufs])
-        _lib.check(L.tv_engine_op_outputs_multi_u8(self._h, ctypes.c_void_p(frames.data_ptr()), B, self._ptrs(outputs),
-                                                   len(outputs), _lib.stream_of(self.device), dst, len(bufs)),
-                   "op_outputs")
-        return [(labels[i], L.tv_engine_op_kernel(self._h, B, i).decode(), bufs[i]) for i in range(len(bufs))]
+        _lib.check(call(L, dst, len(bufs)), "op_outputs")
+        return [(L.tv_engine_op_label(self._h, i).decode(), L.tv_engine_op_kernel(self._h, B, i).decode(), t)
+                for i, t in enumerate(bufs)]
+
+    def profile_multi_u8(self, frames, outputs, cap=4096):
+        """profile_multi() over the buffers of forward_multi_u8."""
+        return self._profile_rows(frames.shape[0], lambda L, *timing: L.tv_engine_profile_multi_u8(
+            self._h, ctypes.c_void_p(frames.data_ptr()), frames.shape[0], self._ptrs(outputs), len(outputs),
+            _lib.stream_of(self.device), *timing), cap)
+
+    def op_outputs_multi_u8(self, frames, outputs):
+        """op_outputs_multi() over the buffers of forward_multi_u8: [(label, kernel, tensor-or-None)] per op."""
+        return self._tap(frames.shape[0], lambda L, *taps: L.tv_engine_op_outputs_multi_u8(
+            self._h, ctypes.c_void_p(frames.data_ptr()), frames.shape[0], self._ptrs(outputs), len(outputs),
+            _lib.stream_of(self.device), *taps))
 
     def profile_multi(self, inputs, outputs, cap=4096):
         """profile() over the buffers of forward_multi."""
         B = inputs[0].shape[0]
-        ms = (ctypes.c_float * cap)()
-        fl = (ctypes.c_double * cap)()
-        n = ctypes.c_int32()
-        L = _lib.lib()
-        _lib.check(L.tv_engine_profile_multi(self._h, self._ptrs(inputs), len(inputs), self._ptrs(outputs), len(outputs),
-                                             B, _lib.stream_of(self.device), ms, fl, cap, ctypes.byref(n)), "profile")
-        return [(L.tv_engine_op_label(self._h, i).decode(), ms[i], fl[i], L.tv_engine_op_kernel(self._h, B, i).decode())
-                for i in range(min(n.value, cap))]
+        return self._profile_rows(B, lambda L, *timing: L.tv_engine_profile_multi(
+            self._h, self._ptrs(inputs), len(inputs), self._ptrs(outputs), len(outputs), B,
+            _lib.stream_of(self.device), *timing), cap)
 
     def forward_u8(self, frames, out=None):
         """frames: uint8 NHWC RGB on this device (ToTensor + ImageNet Normalize fused)."""
@@ -222,32 +225,16 @@ class NativeEngine:
         x = x.contiguous()  # (the library reads through the raw pointer)
         if out is None:
             out = self.alloc_out(B)
-        shapes = self.op_shapes(B)
-        cdt = {2: torch.float16 if self.desc.compute_dtype == 1 else torch.bfloat16, 4: torch.float32}
-        L = _lib.lib()
-        labels = [L.tv_engine_op_label(self._h, i).decode() for i in range(len(shapes))]
-        bufs = [torch.empty((B, h, w, c), dtype=cdt[eb], device=self.device) if eb else None
-                for (h, w, c, eb) in shapes]
-        dst = (ctypes.c_void_p * len(bufs))(*[None if t is None else t.data_ptr() for t in bufs])
-        _lib.check(L.tv_engine_op_outputs(self._h, ctypes.c_void_p(x.data_ptr()), 1 if x.dtype == torch.uint8 else 0,
-                                          B, ctypes.c_void_p(out.data_ptr()), _lib.stream_of(self.device), dst,
-                                          len(bufs)), "op_outputs")
-        return [(labels[i], L.tv_engine_op_kernel(self._h, B, i).decode(), bufs[i]) for i in range(len(bufs))]
+        return self._tap(B, lambda L, *taps: L.tv_engine_op_outputs(
+            self._h, ctypes.c_void_p(x.data_ptr()), 1 if x.dtype == torch.uint8 else 0, B,
+            ctypes.c_void_p(out.data_ptr()), _lib.stream_of(self.device), *taps))
 
     def op_outputs_multi(self, inputs, outputs):
         """op_outputs() over the buffers of forward_multi: [(label, kernel, tensor-or-None)] per op."""
         B = inputs[0].shape[0]
-        shapes = self.op_shapes(B)
-        cdt = {2: torch.float16 if self.desc.compute_dtype == 1 else torch.bfloat16, 4: torch.float32}
-        L = _lib.lib()
-        labels = [L.tv_engine_op_label(self._h, i).decode() for i in range(len(shapes))]
-        bufs = [torch.empty((B, h, w, c), dtype=cdt[eb], device=self.device) if eb else None
-                for (h, w, c, eb) in shapes]
-        dst = (ctypes.c_void_p * len(bufs))(*[None if t is None else t.data_ptr() for t in bufs])
-        _lib.check(L.tv_engine_op_outputs_multi(self._h, self._ptrs(inputs), len(inputs), self._ptrs(outputs),
-                                                len(outputs), B, _lib.stream_of(self.device), dst, len(bufs)),
-                   "op_outputs")
-        return [(labels[i], L.tv_engine_op_kernel(self._h, B, i).decode(), bufs[i]) for i in range(len(bufs))]
+        return self._tap(B, lambda L, *taps: L.tv_engine_op_outputs_multi(
+            self._h, self._ptrs(inputs), len(inputs), self._ptrs(outputs), len(outputs), B,
+            _lib.stream_of(self.device), *taps))
 
     def profile(self, img, out=None, cap=4096):
         """Per-launch (label, ms, flops, kernel) of one forward, timed with HIP events. `img` is the
@@ -255,12 +242,7 @@ class NativeEngine:
         B = img.shape[0]
         if out is None:
             out = self.alloc_out(B)
-        ms = (ctypes.c_float * cap)()
-        fl = (ctypes.c_double * cap)()
-        n = ctypes.c_int32()
-        L = _lib.lib()
-        fn = L.tv_engine_profile_u8 if img.dtype == torch.uint8 else L.tv_engine_profile
-        _lib.check(fn(self._h, ctypes.c_void_p(img.data_ptr()), B, ctypes.c_void_p(out.data_ptr()),
-                                       _lib.stream_of(self.device), ms, fl, cap, ctypes.byref(n)), "profile")
-        return [(L.tv_engine_op_label(self._h, i).decode(), ms[i], fl[i], L.tv_engine_op_kernel(self._h, B, i).decode())
-                for i in range(min(n.value, cap))]
+        return self._profile_rows(B, lambda L, *timing: (
+            L.tv_engine_profile_u8 if img.dtype == torch.uint8 else L.tv_engine_profile)(
+                self._h, ctypes.c_void_p(img.data_ptr()), B, ctypes.c_void_p(out.data_ptr()),
+                _lib.stream_of(self.device), *timing), cap)

@@ -156,8 +156,7 @@ def _host_depth(depth, B):
 
 
 def _device_for(*tensors):
-    if not torch.cuda.is_available():
-        raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
+    _lib.require_gpu()
     for t in tensors:
         if isinstance(t, torch.Tensor) and t.is_cuda:
             return t.device

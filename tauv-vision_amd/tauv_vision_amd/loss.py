@@ -31,12 +31,6 @@ class PoseSample:
     size: Optional[torch.Tensor] = None
 
 
-def _device(t):
-    if not torch.cuda.is_available():
-        raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
-    return t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
-
-
 def _as(t, dtype, dev):
     return t.to(device=dev, dtype=dtype).contiguous()
 
@@ -64,7 +58,7 @@ def _out_shape(model_config):
 def generate_heatmap(truth, model_config, train_config, object_config) -> torch.Tensor:
     """loss.py:31-72 -> [B, n_labels, out_h, out_w] fp32 on the GPU."""
     H, W = _out_shape(model_config)
-    dev = _device(truth.valid)
+    dev = _lib.current_cuda(truth.valid)
     B, n_obj = truth.valid.shape
     L = object_config.n_labels
     valid = _as(truth.valid, torch.uint8, dev)
@@ -85,7 +79,7 @@ def generate_keypoint_heatmap(truth, model_config, train_config, object_config):
     """loss.py:75-135 -> (heatmap, affinity_weight [B, n_keypoints, out_h, out_w],
     affinity [B, n_keypoints, 2, out_h, out_w]) fp32 on the GPU."""
     H, W = _out_shape(model_config)
-    dev = _device(truth.keypoint_valid)
+    dev = _lib.current_cuda(truth.keypoint_valid)
     B, n_inst = truth.keypoint_valid.shape
     n_obj = truth.center.shape[1]
     K = object_config.n_keypoints

@@ -19,6 +19,7 @@ import torch.nn as nn
 from . import _lib
 from .dla import populate
 from .engine import NativeEngine
+from .native import NativeModule
 from .weights import model_io, param_layout, protonet_desc, resnet18_desc, yolact_desc, yolact_head_desc
 
 
@@ -60,7 +61,7 @@ def _head_desc(in_depths, sizes, config, precision, fpn_only=False):
                             _head_layers(config), precision, fpn_only)
 
 
-class Masknet(nn.Module):
+class Masknet(NativeModule):
     """masknet.py:8-55: fpn[0] [B, F, H, W] -> prototypes [B, k, 4H, 4W] (LeakyReLU output).
 
     Parameters keep the reference key layout (`_layers_1.0.0.weight`, `_upsample_layer_1.weight`,
@@ -75,41 +76,20 @@ class Masknet(nn.Module):
         super().__init__()
         self.feature_depth = int(config.feature_depth)
         self.n_prototype_masks = int(config.n_prototype_masks)
-        if precision not in _lib.DTYPES:
-            raise ValueError(f"precision must be one of {sorted(_lib.DTYPES)}")
-        self.precision = precision
+        self._init_native(precision)
         layout = param_layout(protonet_desc(self.feature_depth, self.n_prototype_masks))
         populate(self, layout, seed_layout=layout)
-        self._version = 0
-        self._engines = {}
-        self.register_load_state_dict_post_hook(lambda module, keys: module.invalidate())
-
-    def invalidate(self):
-        self._version += 1
-        self._engines = {}
-
-    def _apply(self, fn, *args, **kwargs):
-        r = super()._apply(fn, *args, **kwargs)
-        self.invalidate()
-        return r
 
     def engine(self, device: torch.device, fpn_h: int, fpn_w: int) -> NativeEngine:
-        key = (device.index if device.index is not None else torch.cuda.current_device(), fpn_h, fpn_w,
-               self.precision, self._version)
-        eng = self._engines.get(key)
-        if eng is None:
-            desc = protonet_desc(self.feature_depth, self.n_prototype_masks, fpn_h, fpn_w, self.precision)
-            eng = NativeEngine(desc, self.state_dict(), key[0])
-            self._engines = {key: eng}
-        return eng
+        return self._engine(device, (fpn_h, fpn_w),
+                            lambda: protonet_desc(self.feature_depth, self.n_prototype_masks, fpn_h, fpn_w,
+                                                  self.precision), self.state_dict)
 
     def forward_nhwc(self, fpn_output: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The native result: fp32 NHWC [B, 4H, 4W, k rounded up to 4]."""
         if fpn_output.dim() != 4 or fpn_output.shape[1] != self.feature_depth:
             raise ValueError(f"expected fpn_output [batch, {self.feature_depth}, H, W], got {tuple(fpn_output.shape)}")
-        if not torch.cuda.is_available():
-            raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
-        dev = fpn_output.device if fpn_output.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        dev = _lib.current_cuda(fpn_output)
         x = fpn_output.to(dev, torch.float32).contiguous()
         return self.engine(dev, x.shape[2], x.shape[3]).forward(x, out)
 
@@ -142,11 +122,7 @@ def _boxes_op(fn, name, a: torch.Tensor, anchor: torch.Tensor, config, out=None)
     anc = _f32(anchor, "anchor").to(x.device)
     if x.dim() != 3 or x.shape[-1] != 4 or anc.dim() != 3 or anc.shape[1:] != x.shape[1:]:
         raise ValueError(f"{name}: {tuple(x.shape)} / anchors {tuple(anc.shape)} mismatch")
-    if out is None:
-        out = torch.empty_like(x)
-    elif tuple(out.shape) != tuple(x.shape) or out.dtype != torch.float32 or not out.is_contiguous() \
-            or out.device != x.device:
-        raise ValueError(f"{name}: out must be a contiguous fp32 {list(x.shape)} tensor on {x.device}")
+    out = _lib.check_out(out, x.shape, x.device, name)
     B, A, _ = x.shape
     _lib.check(fn(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(anc.data_ptr()), B, A, anc.shape[0],
                   float(config.box_variances[0]), float(config.box_variances[1]), ctypes.c_void_p(out.data_ptr()),
@@ -249,17 +225,6 @@ def assemble_mask(mask_prototype: torch.Tensor, mask_coeff: torch.Tensor,
     return out
 
 
-def _check_out(out, shape, device, what):
-    """A caller-supplied output: the kernel writes [B, n, H, W] fp32 through its raw pointer."""
-    if out is None:
-        return torch.empty(shape, dtype=torch.float32, device=device)
-    if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous() \
-            or out.device != device:
-        raise ValueError(f"{what}: out must be a contiguous fp32 {list(shape)} tensor on {device}, got "
-                         f"{out.dtype} {list(out.shape)} on {out.device}")
-    return out
-
-
 def _on(t, device, what):
     if t.device != device:
         raise ValueError(f"{what} is on {t.device}, the prototypes on {device}")
@@ -290,7 +255,7 @@ def assemble_masks(mask_prototype: torch.Tensor, mask_coeff: torch.Tensor, box: 
                 or not counts.is_contiguous():
             raise ValueError("assemble_masks: counts must be a contiguous int32 [B] tensor on the prototypes' device")
         cptr = ctypes.c_void_p(counts.data_ptr())
-    out = _check_out(out, (B, n, H, W), proto.device, "assemble_masks")
+    out = _lib.check_out(out, (B, n, H, W), proto.device, "assemble_masks")
     _lib.check(_lib.lib().tv_yolact_assemble_masks(ctypes.c_void_p(proto.data_ptr()), _lib.strides(proto, 4), B, K, H, W,
                                                    ctypes.c_void_p(coeff.data_ptr()), bptr, cptr, n,
                                                    ctypes.c_void_p(out.data_ptr()), _lib.stream_of(proto.device)),
@@ -324,7 +289,7 @@ def assemble_masks_indexed(mask_prototype: torch.Tensor, mask_coeff: torch.Tenso
         if box.shape != (B, A, 4):
             raise ValueError(f"assemble_masks_indexed: box {tuple(box.shape)} must be [{B}, {A}, 4]")
         bptr = ctypes.c_void_p(box.data_ptr())
-    out = _check_out(out, (B, n, H, W), proto.device, "assemble_masks_indexed")
+    out = _lib.check_out(out, (B, n, H, W), proto.device, "assemble_masks_indexed")
     _lib.check(_lib.lib().tv_yolact_assemble_masks_indexed(
         ctypes.c_void_p(proto.data_ptr()), _lib.strides(proto, 4), B, K, H, W, ctypes.c_void_p(coeff.data_ptr()), bptr,
         A, ctypes.c_void_p(det.data_ptr()), ctypes.c_void_p(counts.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
@@ -362,18 +327,17 @@ def detection_records(classification: torch.Tensor, box: torch.Tensor, det: torc
     if C1 < 2 or A < 1 or A > 1 << 24:
         raise ValueError("detection_records: need >= 2 classes (with the background) and 1 <= anchors <= 2^24 "
                          "(the anchor index is stored as fp32)")
-    if not torch.cuda.is_available():
-        raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
+    _lib.require_gpu()
     dev = classification.device
     for t, name in ((classification, "classification"), (box, "box"), (det, "det"), (counts, "counts")):
         if not t.is_cuda or t.device != dev:
             raise ValueError(f"detection_records: {name} is on {t.device}; every tensor must be on one CUDA device")
         if not t.is_contiguous():
             raise ValueError(f"detection_records: {name} must be contiguous")
-    out = _check_out(out, (B, n, REC), dev, "detection_records")
+    out = _lib.check_out(out, (B, n, REC), dev, "detection_records")
     cptr = None
     if confidence_out is not None:
-        confidence_out = _check_out(confidence_out, (B, n, C1), dev, "detection_records confidence")
+        confidence_out = _lib.check_out(confidence_out, (B, n, C1), dev, "detection_records confidence")
         cptr = ctypes.c_void_p(confidence_out.data_ptr())
     _lib.check(_lib.lib().tv_yolact_detection_records(
         ctypes.c_void_p(classification.data_ptr()), ctypes.c_void_p(box.data_ptr()), ctypes.c_void_p(det.data_ptr()),
@@ -390,56 +354,23 @@ def yolact_head_state_dict(state_dict):
     return {k: v for k, v in state_dict.items() if not k.startswith("_backbone.")}
 
 
-class _NativeNet(nn.Module):
-    """Reference-layout parameters + the cache of native engines built from them (one per device,
-    map sizes and precision), dropped whenever the parameters may have changed."""
-
-    def _init_native(self, precision):
-        if precision not in _lib.DTYPES:
-            raise ValueError(f"precision must be one of {sorted(_lib.DTYPES)}")
-        self.precision = precision
-        self._version = 0
-        self._engines = {}
-        self.register_load_state_dict_post_hook(lambda module, keys: module.invalidate())
-
-    def invalidate(self):
-        self._version += 1
-        self._engines = {}
-
-    def _apply(self, fn, *args, **kwargs):
-        r = super()._apply(fn, *args, **kwargs)
-        self.invalidate()
-        return r
-
-    def _maps(self, backbone_outputs, in_depths):
-        """The backbone maps as contiguous fp32 NCHW tensors of one CUDA device and batch; refuses
-        anything else before a launch."""
-        maps = tuple(backbone_outputs)
-        if len(maps) != len(in_depths):
-            raise ValueError(f"expected {len(in_depths)} backbone maps, got {len(maps)}")
-        if not torch.cuda.is_available():
-            raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
-        dev, B = maps[0].device, maps[0].shape[0]
-        out = []
-        for i, (m, c) in enumerate(zip(maps, in_depths)):
-            if m.dim() != 4 or m.shape[1] != c or m.shape[0] != B:
-                raise ValueError(f"backbone map {i}: expected [{B}, {c}, H, W], got {tuple(m.shape)}")
-            if m.device != dev or not m.is_cuda:
-                raise ValueError(f"backbone map {i} is on {m.device}; every map must be on one CUDA device "
-                                 f"(map 0 is on {dev})")
-            out.append(m.to(torch.float32).contiguous())
-        return out
-
-    def _engine(self, key, make_desc, state_dict):
-        key = key + (self.precision, self._version_key())
-        eng = self._engines.get(key)
-        if eng is None:
-            eng = NativeEngine(make_desc(), state_dict(), key[0])
-            self._engines = {key: eng}
-        return eng
-
-    def _version_key(self):
-        return self._version
+def _maps(backbone_outputs, in_depths):
+    """The backbone maps as contiguous fp32 NCHW tensors of one CUDA device and batch; refuses
+    anything else before a launch."""
+    maps = tuple(backbone_outputs)
+    if len(maps) != len(in_depths):
+        raise ValueError(f"expected {len(in_depths)} backbone maps, got {len(maps)}")
+    _lib.require_gpu()
+    dev, B = maps[0].device, maps[0].shape[0]
+    out = []
+    for i, (m, c) in enumerate(zip(maps, in_depths)):
+        if m.dim() != 4 or m.shape[1] != c or m.shape[0] != B:
+            raise ValueError(f"backbone map {i}: expected [{B}, {c}, H, W], got {tuple(m.shape)}")
+        if m.device != dev or not m.is_cuda:
+            raise ValueError(f"backbone map {i} is on {m.device}; every map must be on one CUDA device "
+                             f"(map 0 is on {dev})")
+        out.append(m.to(torch.float32).contiguous())
+    return out
 
 
 def _outputs(out, shapes, device, what):
@@ -449,10 +380,10 @@ def _outputs(out, shapes, device, what):
     out = list(out)
     if len(out) != len(shapes):
         raise ValueError(f"{what}: out must hold {len(shapes)} tensors, got {len(out)}")
-    return [_check_out(o, s, device, f"{what} out[{i}]") for i, (o, s) in enumerate(zip(out, shapes))]
+    return [_lib.check_out(o, s, device, f"{what} out[{i}]") for i, (o, s) in enumerate(zip(out, shapes))]
 
 
-class FeaturePyramid(_NativeNet):
+class FeaturePyramid(NativeModule):
     """feature_pyramid.py:8-58: the backbone maps (c3, c4, c5) -> the tuple of len(in_depths) +
     n_fpn_downsample_layers maps [B, F, h, w]. Parameters keep the reference keys
     (`_lateral_layers.i.*`, `_downsample_layers.i.*`, `_prediction_layers.i.*`). One native call:
@@ -468,12 +399,14 @@ class FeaturePyramid(_NativeNet):
         layout = param_layout(_head_desc(self.in_depths, [(1, 1)] * len(self.in_depths), config, "fp32", True))
         populate(self, layout, seed_layout=layout)
 
+    def engine(self, device, sizes):
+        return self._engine(device, (tuple(sizes),),
+                            lambda: _head_desc(self.in_depths, sizes, self.config, self.precision, True), self.state_dict)
+
     def forward_nhwc(self, backbone_outputs, out=None):
-        maps = self._maps(backbone_outputs, self.in_depths)
-        sizes = tuple((m.shape[2], m.shape[3]) for m in maps)
+        maps = _maps(backbone_outputs, self.in_depths)
         dev = maps[0].device
-        eng = self._engine((dev.index, sizes), lambda: _head_desc(self.in_depths, sizes, self.config, self.precision, True),
-                           self.state_dict)
+        eng = self.engine(dev, tuple((m.shape[2], m.shape[3]) for m in maps))
         B = maps[0].shape[0]
         outs = _outputs(out, [(B, h, w, cp) for h, w, _, cp in model_io(eng.desc)[1]], dev, "FeaturePyramid")
         eng.forward_multi(maps, outs)
@@ -483,7 +416,7 @@ class FeaturePyramid(_NativeNet):
         return tuple(o.permute(0, 3, 1, 2) for o in self.forward_nhwc(backbone_outputs, out))
 
 
-class PredictionHead(_NativeNet):
+class PredictionHead(NativeModule):
     """prediction_head.py:9-143: the parameters of the one head shared by every FPN level, in the
     reference layout (the Bottleneck blocks as torchvision's: conv1, bn1, conv2, bn2, conv3, bn3,
     bias-free convs). It runs inside YolactHead's native plan, once per level with the same weights;
@@ -503,7 +436,7 @@ class PredictionHead(_NativeNet):
                            "neck, every level's head and the protonet); call YolactHead((c3, c4, c5))")
 
 
-class YolactHead(_NativeNet):
+class YolactHead(NativeModule):
     """Everything of Yolact.forward after the backbone (model.py:34-60): (c3, c4, c5) ->
     (classification [B, A, C+1], box_encoding [B, A, 4], mask_coeff [B, A, k], anchor [1, A, 4],
     mask_prototype [B, k, 4h, 4w]), all fp32, in one native call. The three anchor-indexed tensors are
@@ -536,14 +469,10 @@ class YolactHead(_NativeNet):
         """The head's one precision. The sub-modules are used here as parameter holders: their own
         `precision` and engine caches serve only a direct call of `_feature_pyramid(...)` or
         `_masknet(...)`, never this module's forward; they are kept equal to the head's."""
-        if precision not in _lib.DTYPES:
-            raise ValueError(f"precision must be one of {sorted(_lib.DTYPES)}")
-        for m in (self, self._feature_pyramid, self._masknet, self._prediction_head):
-            m.precision = precision
-            m.invalidate()
-
-    def _version_key(self):
-        return (self._version, self._feature_pyramid._version, self._masknet._version, self._prediction_head._version)
+        for m in self.modules():
+            if isinstance(m, NativeModule):
+                NativeModule.set_precision(m, precision)
+        return self
 
     def head_state_dict(self):
         return yolact_head_state_dict(self.state_dict())
@@ -566,11 +495,11 @@ class YolactHead(_NativeNet):
         return out
 
     def engine(self, device, sizes):
-        return self._engine((device.index, tuple(sizes)),
+        return self._engine(device, (tuple(sizes),),
                             lambda: _head_desc(self.in_depths, sizes, self.config, self.precision), self.head_state_dict)
 
     def forward(self, backbone_outputs, out=None):
-        maps = self._maps(backbone_outputs, self.in_depths)
+        maps = _maps(backbone_outputs, self.in_depths)
         sizes = tuple((m.shape[2], m.shape[3]) for m in maps)
         levels = self.level_sizes(sizes)
         if len(levels) > len(self.config.anchor_scales):
@@ -589,8 +518,7 @@ def _image(img):
     before a launch."""
     if img.dim() != 4 or img.shape[1] != 3:
         raise ValueError(f"expected img [batch, 3, in_h, in_w], got {tuple(img.shape)}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
+    _lib.require_gpu()
     if not img.is_cuda:
         raise ValueError(f"img is on {img.device}; it must be on a CUDA device")
     return img.to(torch.float32).contiguous()
@@ -630,12 +558,11 @@ def _frames(frames, size, config):
 
 def _frames_on_gpu(frames):
     """The frames, contiguous, on their CUDA device (the current one for host frames)."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
+    _lib.require_gpu()
     return (frames if frames.is_cuda else frames.cuda()).contiguous()
 
 
-class Resnet101Backbone(_NativeNet):
+class Resnet101Backbone(NativeModule):
     """yolact/model/backbone.py:9-32 (the reference's class name; the network is torchvision's
     resnet18): img [B, 3, H, W] -> (c3, c4, c5), the outputs of layer2.1.bn2, layer3.1.bn2 and
     layer4.1.bn2 — each the last block's second BatchNorm, before the residual add and the ReLU —
@@ -674,9 +601,13 @@ class Resnet101Backbone(_NativeNet):
         n = len("_feature_extractor.")
         return {k[n:]: v for k, v in self.state_dict().items()}
 
+    def engine(self, device, in_h, in_w):
+        return self._engine(device, (in_h, in_w), lambda: resnet18_desc(in_h, in_w, self.precision),
+                            self.backbone_state_dict)
+
     def _run(self, x, H, W, out, u8):
         B, dev = x.shape[0], x.device
-        eng = self._engine((dev.index, (H, W)), lambda: resnet18_desc(H, W, self.precision), self.backbone_state_dict)
+        eng = self.engine(dev, H, W)
         outs = _outputs(out, [(B, h, w, cp) for h, w, _, cp in model_io(eng.desc)[1]], dev, "Resnet101Backbone")
         if u8:
             eng.forward_multi_u8(x, outs)
@@ -729,15 +660,6 @@ class Yolact(YolactHead):
     def _native(self):
         return isinstance(getattr(self, "_backbone", None), Resnet101Backbone)
 
-    def set_precision(self, precision: str):
-        super().set_precision(precision)
-        if self._native():  # (the backbone's own precision serves a direct call of it; kept equal)
-            self._backbone.precision = precision
-            self._backbone.invalidate()
-
-    def _version_key(self):
-        return super()._version_key() + ((self._backbone._version,) if self._native() else ())
-
     def forward(self, img, out=None):
         if getattr(self, "_backbone", None) is None:
             raise RuntimeError("Yolact was built without a backbone: the ResNet is not part of this library. Pass "
@@ -754,7 +676,7 @@ class Yolact(YolactHead):
         if len(levels) > len(self.config.anchor_scales):
             raise ValueError(f"{len(levels)} FPN levels but {len(self.config.anchor_scales)} anchor_scales")
         c = self.config
-        eng = self._engine((dev.index, ("img", H, W)),
+        eng = self._engine(dev, ("img", H, W),
                            lambda: yolact_desc(H, W, int(c.feature_depth), int(c.n_fpn_downsample_layers),
                                                int(c.n_classes), int(c.n_prototype_masks),
                                                len(c.anchor_aspect_ratios), _head_layers(c), self.precision),
@@ -871,8 +793,7 @@ class YolactDetector:
         self.model, self.B, self.top_k = model, int(B), int(top_k)
         self.frame_hw = (int(frame_hw[0]), int(frame_hw[1]))
         self.size = self.frame_hw if size is None else (int(size[0]), int(size[1]))
-        if not torch.cuda.is_available():
-            raise RuntimeError("tauv_vision_amd needs a gfx950 (MI355X) GPU; no HIP device is visible")
+        _lib.require_gpu()
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError(f"YolactDetector needs a GPU device, got {self.device}")

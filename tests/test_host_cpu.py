@@ -87,10 +87,10 @@ def test_module_state_dict_layout_and_load():
     keys = [(k, tuple(v.shape)) for k, v in model.state_dict().items()]
     assert keys == [(k, tuple(s)) for k, s in models_index()[case["name"]]["keys"]]
     sd = case_state_dict(case["name"])
-    v0 = model._version[0]
+    v0 = model._params_version
     res = model.load_state_dict(sd, strict=True)
     assert not res.missing_keys and not res.unexpected_keys
-    assert model._version[0] > v0
+    assert model._params_version > v0
     for k, v in model.state_dict().items():
         assert torch.equal(v, sd[k])
 

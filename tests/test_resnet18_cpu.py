@@ -54,9 +54,9 @@ def test_strict_loading_both_ways():
     assert [(k, tuple(v.shape)) for k, v in bb.state_dict().items()] == \
         [("_feature_extractor." + k, s) for k, s in ref_layout()]
     sd = rr.seeded_resnet18_state_dict(3)
-    v0 = bb._version
+    v0 = bb._params_version
     bb.load_state_dict({"_feature_extractor." + k: v for k, v in sd.items()}, strict=True)
-    assert bb._version != v0
+    assert bb._params_version != v0
     for k, v in sd.items():
         assert torch.equal(bb.state_dict()["_feature_extractor." + k], v)
     ref = rr.ResNet18Ref()
