@@ -405,6 +405,34 @@ int tv_localize_masks(const float* masks, int32_t mh, int32_t mw, const int32_t*
                       int32_t dh, int32_t dw, int32_t bound_by_box, double fx, double fy, double cx, double cy,
                       double min_depth_sum, double min_z, float* out, void* stream);
 
+/* The greedy keypoint-to-object matching of decode_keypoints() (decode.py:100-135) for B images in
+ * one launch, on what tv_decode (mode 1) writes. Device pointers, async on `stream`, no workspace,
+ * no host synchronisation (graph-capturable).
+ * obj_records [B, K, 10] with obj_counts [B]; kp_records [B, K_kp, 10] with kp_counts [B] (label in
+ * column 0, y, x in 2, 3, the affinity pair ay, ax in 8, 9); owner_label / owner_slot int32
+ * [n_keypoints]: the object label and that object's keypoint slot of each flat keypoint index
+ * (ObjectConfigSet.decode_keypoint_index); max_slots: the most keypoints any object has.
+ * The keypoints of image b are taken in rank order 0 .. kp_counts[b]-1 (the record order is the
+ * reference's score order, the count its `break`). The candidates of keypoint k with label kl are the
+ * object records d < obj_counts[b] with label == owner_label[kl] whose slot owner_slot[kl] is still
+ * free; without one, k stays unmatched. Otherwise err[d] = |atan2(ay, ax) - atan2(ky - y_d, kx - x_d)|
+ * in double on the fp32 record values (the reference's Python floats; no wrap-around handling, as
+ * there), the candidate of the smallest error wins, the smaller rank on a tie (errs.index(min(errs))),
+ * the first candidate when the affinity is NaN (every error is NaN then), and its slot becomes taken.
+ * A keypoint label outside [0, n_keypoints), or an owner slot outside [0, max_slots), has no candidate.
+ * Outputs, every element written by every call:
+ *   kp_det [B, K_kp] int32   the object rank keypoint k went to; -1 if unmatched or k >= kp_counts[b]
+ *   slot_kp [B, K, max_slots] int32   the keypoint rank held by (object, slot), or -1
+ *   n_matched [B, K] int32   the number of slots of the object that are held
+ * One workgroup per image: the K_kp x K errors are computed in parallel into an LDS table when
+ * K_kp * K <= 4096, inside the serial walk otherwise, with identical results.
+ * TV_EINVAL before any launch: null pointers, B < 0, n_keypoints < 1, max_slots outside 1..32,
+ * K outside 1..256, K_kp outside 1..1024. B == 0 succeeds and launches nothing. */
+int tv_match_keypoints(const float* obj_records, const int32_t* obj_counts, const float* kp_records,
+                       const int32_t* kp_counts, const int32_t* owner_label, const int32_t* owner_slot,
+                       int32_t n_keypoints, int32_t max_slots, int32_t B, int32_t K, int32_t K_kp, int32_t* kp_det,
+                       int32_t* slot_kp, int32_t* n_matched, void* stream);
+
 /* Training targets of the CenterNet loss (loss.py:31-135), fp32, device pointers, async on `stream`.
  * generate_heatmap (loss.py:31-72): valid [B,n_objects] u8 (bool), label [B,n_objects] int64,
  *   center [B,n_objects,2] fp32 (y, x normalised) -> heatmap [B,n_labels,in_h/ratio,in_w/ratio]:

@@ -500,6 +500,15 @@ int tv_localize_masks(const float* masks, int32_t mh, int32_t mw, const int32_t*
                                           (hipStream_t)stream); })
 }
 
+int tv_match_keypoints(const float* obj_records, const int32_t* obj_counts, const float* kp_records,
+                       const int32_t* kp_counts, const int32_t* owner_label, const int32_t* owner_slot,
+                       int32_t n_keypoints, int32_t max_slots, int32_t B, int32_t K, int32_t K_kp, int32_t* kp_det,
+                       int32_t* slot_kp, int32_t* n_matched, void* stream) {
+  TV_GUARD({ return launch_match_keypoints(obj_records, obj_counts, kp_records, kp_counts, owner_label, owner_slot,
+                                           n_keypoints, max_slots, B, K, K_kp, kp_det, slot_kp, n_matched,
+                                           (hipStream_t)stream); })
+}
+
 int tv_decode_workspace_size(int32_t B, int32_t C, int32_t H, int32_t W, int32_t K, int64_t* bytes) {
   if (!bytes || B < 1 || C < 1 || H < 1 || W < 1 || K < 1) { set_error("bad argument"); return TV_EINVAL; }
   *bytes = (int64_t)decode_workspace_bytes(B, C, H, W, K);

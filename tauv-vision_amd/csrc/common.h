@@ -446,6 +446,13 @@ int launch_localize_masks(const float* masks, int mh, int mw, const int* counts,
                           int A, int B, int n, const uint16_t* depth, int depth_batch, int dh, int dw, int bound_by_box,
                           double fx, double fy, double cx, double cy, double min_depth_sum, double min_z, float* out,
                           hipStream_t s);
+// Keypoint-to-object matching of decode_keypoints (keypoints.hip) on tv_decode's mode-1 records: the
+// contract is tv_match_keypoints' in include/tauv_vision_amd.h. Arguments are checked here (return 1
+// with the error text set); B == 0 launches nothing.
+int launch_match_keypoints(const float* obj_records, const int* obj_counts, const float* kp_records,
+                           const int* kp_counts, const int* owner_label, const int* owner_slot, int n_keypoints,
+                           int max_slots, int B, int K, int K_kp, int* kp_det, int* slot_kp, int* n_matched,
+                           hipStream_t s);
 int launch_uncovered_copy(const void* add, int add_ldc, void* out, int out_ldc, int C, int B,
                           int tH, int tW, int y0, int y1, int x0, int x1, int dtype,
                           hipStream_t s);

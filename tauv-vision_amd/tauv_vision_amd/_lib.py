@@ -97,6 +97,8 @@ EXPORTS = {
                            c_f64, c_f64, c_f64, c_vp, c_vp], c_i32),
     "tv_localize_masks": ([c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32,
                            c_i32, c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_vp, c_vp], c_i32),
+    "tv_match_keypoints": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
+                            c_vp], c_i32),
     "tv_train_heatmap": ([c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_vp, c_vp], c_i32),
     "tv_train_keypoint_targets": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                    c_f64, c_f64, c_vp, c_vp, c_vp, c_vp], c_i32),

@@ -10,7 +10,7 @@ slices of one fp32 NHWC head tensor (same shapes and values, different strides).
 import ctypes
 import threading
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -104,6 +104,7 @@ class _NativeModel(NativeModule):
     def invalidate(self):
         super().invalidate()
         self._graphs = {}
+        self._detectors = {}
 
     def _device_for(self, t: torch.Tensor) -> torch.device:
         """`t`'s GPU; a host tensor goes to the parameters' GPU (the current one if they are on the host)."""
@@ -197,6 +198,159 @@ class _NativeModel(NativeModule):
         from .decode import decode
         return decode(self.forward_frames(frames, (model_config.in_h, model_config.in_w)), model_config,
                       n_detections, score_threshold)
+
+    def detect_keypoints(self, frames, model_config, n_detections: int = 10, keypoint_n_detections: int = 50,
+                         score_threshold: float = 0.6, keypoint_score_threshold: float = 0.3, depth=None, camera=None,
+                         M_projection=None):
+        """The CenterNet node's callback from the camera frames to the matched keypoints and the 3-D
+        points (centernet_node.py:90-178) in one call: uint8 RGB frames [B, H, W, 3] (or [H, W, 3]) of
+        any size, resized to (model_config.in_h, model_config.in_w), through a cached CenternetDetector.
+        depth (uint16 millimetres, [dh, dw] or [B, dh, dw], numpy or torch) with camera = (fx, fy, cx,
+        cy), or with M_projection (the node's matrix: fx, fy, cx, cy = M[0,0], M[1,1], M[0,2], M[1,2]),
+        also localises every object. Returns CenternetDetections of host tensors (points None without
+        depth). One device-to-host synchronisation. The defaults are the node's (:116-117, :124)."""
+        from .localize import _host_depth
+        from .yolact import _frames, _frames_on_gpu
+        frames, _ = _frames(frames, None, None)
+        if camera is None and M_projection is not None and depth is not None:
+            import numpy as np
+            M = np.asarray(M_projection, dtype=np.float64)
+            if M.ndim != 2 or M.shape[0] < 2 or M.shape[1] < 3:
+                raise ValueError(f"M_projection must be at least 2 x 3, got {list(M.shape)}")
+            camera = (float(M[0, 0]), float(M[1, 1]), float(M[0, 2]), float(M[1, 2]))
+        if (depth is None) != (camera is None):
+            raise ValueError("depth goes with camera = (fx, fy, cx, cy) or M_projection")
+        if camera is not None and len(camera) != 4:
+            raise ValueError(f"camera must be (fx, fy, cx, cy), got {camera}")
+        B = frames.shape[0]
+        if depth is not None:
+            depth = _host_depth(depth, max(B, 1))
+        frames = _frames_on_gpu(frames)
+        dev = frames.device
+        hw = (frames.shape[1], frames.shape[2])
+        key = (dev.index, B, hw, int(model_config.in_h), int(model_config.in_w), int(n_detections),
+               int(keypoint_n_detections), self.precision, self._version_key())
+        det = getattr(self, "_detectors", {}).get(key)
+        if det is None:
+            det = CenternetDetector(self, B, hw, model_config, n_detections, keypoint_n_detections, dev)
+            self._detectors = {key: det}
+        with torch.cuda.device(dev):
+            det(frames, score_threshold, keypoint_score_threshold, None if depth is None else depth.to(dev), camera)
+            return CenternetDetections(*[None if t is None else t.clone() for t in det.host()])
+
+
+class CenternetDetections(NamedTuple):
+    """KeypointRecords' arrays (decode.py: `records` [B, K, 10] / `counts` [B] of the objects,
+    `keypoint_records` [B, K_kp, 10] / `keypoint_counts` [B], `slot_kp` [B, K, max_slots], `n_matched`
+    [B, K], `kp_det` [B, K_kp]) plus `points` [B, K, 8] fp32 (DeviceLocalizer's x, y, z, valid, n_pixels,
+    depth_sum, e_x, e_y per object) or None without depth."""
+    records: torch.Tensor
+    counts: torch.Tensor
+    keypoint_records: torch.Tensor
+    keypoint_counts: torch.Tensor
+    slot_kp: torch.Tensor
+    n_matched: torch.Tensor
+    kp_det: torch.Tensor
+    points: Optional[torch.Tensor]
+
+
+class CenternetDetector:
+    """The CenterNet node's callback (centernet_node.py:90-178) for one (B, frame size) with static device
+    buffers: the engine's forward into `head_out` (from the uint8 frames; frames of another size than
+    (model_config.in_h, in_w) go through `preprocess` into the static fp32 `img` first) ->
+    DeviceKeypointDecoder (object decode, keypoint decode, matching) -> with depth,
+    DeviceLocalizer.boxes on the object records with the node's 0.4 / 10 / 1. `model`: a
+    CenterpointDLA34 or a Centernet whose object config trains keypoints.
+
+    A call launches on the current stream, allocates nothing and never synchronises, and it calls the
+    engine itself (not the module's graph cache): the whole step can be captured in one graph after one
+    eager call on the capture stream. `decoder`'s buffers and `points` [B, K, 8] are overwritten by every
+    call."""
+
+    def __init__(self, model, B, frame_hw, model_config, n_detections=10, keypoint_n_detections=50, device=None):
+        from .decode import DeviceKeypointDecoder
+        from .localize import DeviceLocalizer
+        if not isinstance(model, _NativeModel):
+            raise ValueError("CenternetDetector needs a CenterpointDLA34 or a Centernet")
+        oc = model.object_config
+        if not oc.train_keypoints or oc.n_keypoints < 1:
+            raise ValueError("CenternetDetector needs a model with keypoint heads (object_config.train_keypoints)")
+        if int(B) < 1 or len(frame_hw) != 2 or min(int(v) for v in frame_hw) < 1:
+            raise ValueError(f"CenternetDetector needs B >= 1 and frame_hw = (H, W), got {B}, {frame_hw}")
+        _lib.require_gpu()
+        dev = next(model.parameters()).device if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError(f"CenternetDetector needs a GPU device, got {dev}")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.model, self.model_config, self.B, self.device = model, model_config, int(B), dev
+        self.frame_hw = (int(frame_hw[0]), int(frame_hw[1]))
+        self.size = (int(model_config.in_h), int(model_config.in_w))
+        self.engine = model.engine(dev, *self.size)
+        self.head_out = self.engine.alloc_out(self.B)
+        self.prediction = prediction_from_nhwc(self.head_out, oc)
+        self.img = None if self.size == self.frame_hw else \
+            torch.empty((self.B, 3) + self.size, dtype=torch.float32, device=dev)
+        _, C, H, W = self.prediction.heatmap.shape
+        self.K = int(n_detections)
+        self.decoder = DeviceKeypointDecoder(self.B, C, oc.n_keypoints, H, W, self.K, int(keypoint_n_detections), oc,
+                                             dev)
+        self.localizer = DeviceLocalizer(self.B, self.K, dev)
+        self.points = self.localizer.out
+        self._localized = False
+        self._host = None
+
+    def __call__(self, frames, score_threshold, keypoint_score_threshold, depth=None, camera=None):
+        """frames: uint8 [B, H, W, 3] of the detector's frame size on its device — or the normalised fp32
+        image [B, 3, in_h, in_w] (the fp32 entry, for frames preprocessed elsewhere). depth: uint16
+        millimetres [1 or B, dh, dw] on the device, with camera = (fx, fy, cx, cy). Returns
+        CenternetDetections of the static device buffers (points None without depth)."""
+        if (depth is None) != (camera is None):
+            raise ValueError("depth and camera = (fx, fy, cx, cy) go together")
+        if camera is not None and len(camera) != 4:
+            raise ValueError(f"camera must be (fx, fy, cx, cy), got {camera}")
+        if not isinstance(frames, torch.Tensor) or frames.device != self.device:
+            raise ValueError(f"frames must be a tensor on {self.device}")
+        dec = self.decoder
+        if depth is not None:
+            from .localize import check_boxes_args
+            check_boxes_args(self.B, self.K, dec.records, dec.counts, depth, camera[0], camera[1], self.device)
+        if frames.dtype == torch.float32:
+            if tuple(frames.shape) != (self.B, 3) + self.size or not frames.is_contiguous():
+                raise ValueError(f"the fp32 image must be contiguous {[self.B, 3, *self.size]}, got {list(frames.shape)}")
+            self.engine.forward(frames, self.head_out)
+        else:
+            if frames.dtype != torch.uint8 or tuple(frames.shape) != (self.B,) + self.frame_hw + (3,) \
+                    or not frames.is_contiguous():
+                raise ValueError(f"CenternetDetector built for contiguous uint8 frames {[self.B, *self.frame_hw, 3]}, "
+                                 f"got {frames.dtype} {list(frames.shape)}")
+            if self.img is None:
+                self.engine.forward_u8(frames, self.head_out)
+            else:
+                self.engine.forward(preprocess(frames, self.size[0], self.size[1], out=self.img), self.head_out)
+        res = dec(self.prediction, self.model_config, score_threshold, keypoint_score_threshold)
+        self._localized = depth is not None
+        if self._localized:
+            fx, fy, cx, cy = camera
+            self.localizer.boxes(res.records, res.counts, depth, fx, fy, cx, cy, 0.4, 10.0, 1.0)
+        return CenternetDetections(*res, self.points if self._localized else None)
+
+    def host(self):
+        """CenternetDetections of the last call on the host: the decoder's packed buffer (and the points)
+        copied to pinned memory, one synchronisation. The tensors are views of the detector's pinned
+        mirror, overwritten by the next host()."""
+        dec = self.decoder
+        n = dec.packed.numel()
+        if self._host is None:
+            self._host = torch.empty(n + self.points.numel() * 4, dtype=torch.uint8, pin_memory=True)
+        h = self._host
+        with torch.cuda.device(self.device):
+            h[:n].copy_(dec.packed, non_blocking=True)
+            if self._localized:
+                h[n:].copy_(self.points.view(-1).view(torch.uint8), non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+        pts = h[n:].view(torch.float32).view(tuple(self.points.shape)) if self._localized else None
+        return CenternetDetections(*dec._views(h[:n]), pts)
 
 
 class Centernet(_NativeModel):

@@ -18,7 +18,7 @@ import ctypes
 import threading
 from dataclasses import dataclass
 from math import atan2, pi
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -254,6 +254,193 @@ def decode_keypoints(prediction, model_config, object_config, M_projection, n_de
             best.keypoints[slot] = (ky, kx)
             best.keypoint_affinities[slot] = (ay, ax)
             best.keypoint_scores[slot] = float(r[1])
+        _solve_poses(dets, model_config, object_config, M_projection)
+        out.append(dets)
+    return out
+
+
+MAX_SLOTS = 32  # tv_match_keypoints keeps an object's taken slots in one 32-bit mask
+
+
+class KeypointRecords(NamedTuple):
+    """What decode_keypoints computes, as arrays: `records` [B, K, 10] / `counts` [B] of the objects and
+    `keypoint_records` [B, K_kp, 10] / `keypoint_counts` [B] of the keypoints (tv_decode mode 1: label,
+    score, y, x, h, w, depth, flat index, affinity y, affinity x), `slot_kp` [B, K, max_slots] int32 the
+    keypoint rank held by (object, slot) or -1, `n_matched` [B, K] int32, `kp_det` [B, K_kp] int32 the
+    object rank a keypoint went to or -1 (the contract: tv_match_keypoints in include/tauv_vision_amd.h)."""
+    records: object
+    counts: object
+    keypoint_records: object
+    keypoint_counts: object
+    slot_kp: object
+    n_matched: object
+    kp_det: object
+
+
+def keypoint_owner_tables(object_config):
+    """(owner label, owner slot) int32 lists over the flat keypoint index and the most keypoints any object
+    has. ValueError for an object with more than 32 keypoints, or a config without keypoints."""
+    n = object_config.n_keypoints
+    if n < 1:
+        raise ValueError("the object config has no keypoints")
+    owners = [object_config.decode_keypoint_index(i) for i in range(n)]
+    max_slots = max(len(c.keypoints or []) for c in object_config.configs)
+    if max_slots > MAX_SLOTS:
+        raise ValueError(f"an object has {max_slots} keypoints; the device matching takes at most {MAX_SLOTS}")
+    return [o for o, _ in owners], [s for _, s in owners], max_slots
+
+
+class DeviceKeypointDecoder:
+    """Static-buffer decode_keypoints without the host: the object decode, the keypoint decode and the
+    matching (tv_match_keypoints, csrc/keypoints.hip) launched on the current stream into preallocated
+    device buffers, with no allocation and no host synchronisation — so forward + decode + localisation
+    can be captured in one HIP graph. For a fixed (B, C labels, C_kp keypoint channels, H, W, K, K_kp)
+    and object config. `records`, `counts`, `keypoint_records`, `keypoint_counts`, `slot_kp`, `n_matched`
+    and `kp_det` (KeypointRecords' fields) are views of one allocation `packed`: one copy carries
+    everything. Every element is overwritten by every call."""
+
+    def __init__(self, B, C, C_kp, H, W, K, K_kp, object_config, device):
+        owner_label, owner_slot, S = keypoint_owner_tables(object_config)
+        if C != object_config.n_labels or C_kp != len(owner_label):
+            raise ValueError(f"the object config has {object_config.n_labels} labels and {len(owner_label)} keypoints, "
+                             f"the decoder {C} and {C_kp} channels")
+        if not 1 <= K <= 256 or not 1 <= K_kp <= 1024:
+            raise ValueError(f"the device matching takes 1..256 objects and 1..1024 keypoints per image, got {K}, {K_kp}")
+        _lib.require_gpu()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"DeviceKeypointDecoder needs a GPU device, got {self.device}")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        dev = self.device
+        self.shape = (B, C, C_kp, H, W, K, K_kp)
+        self.max_slots = S
+        self.objects = DeviceDecoder(B, C, H, W, K, dev)
+        self.keypoints = DeviceDecoder(B, C_kp, H, W, K_kp, dev)
+        self.owner_label = torch.tensor(owner_label, dtype=torch.int32).to(dev)
+        self.owner_slot = torch.tensor(owner_slot, dtype=torch.int32).to(dev)
+        sizes = [B * K * REC, B, B * K_kp * REC, B, B * K * S, B * K, B * K_kp]  # 4-byte elements
+        self.packed = torch.zeros(sum(sizes) * 4, dtype=torch.uint8, device=dev)
+        self._offsets = [sum(sizes[:i]) * 4 for i in range(len(sizes) + 1)]
+        self.records, self.counts, self.keypoint_records, self.keypoint_counts, self.slot_kp, self.n_matched, \
+            self.kp_det = self._views(self.packed)
+        # the two decodes write straight into `packed`
+        self.objects.packed, self.objects.records, self.objects.counts = None, self.records, self.counts
+        self.keypoints.packed, self.keypoints.records, self.keypoints.counts = \
+            None, self.keypoint_records, self.keypoint_counts
+        self._host = None
+
+    def _views(self, buf):
+        B, _, _, _, _, K, K_kp = self.shape
+        o = self._offsets
+        f32 = lambda i, *shape: buf[o[i]:o[i + 1]].view(torch.float32).view(*shape)
+        i32 = lambda i, *shape: buf[o[i]:o[i + 1]].view(torch.int32).view(*shape)
+        return KeypointRecords(f32(0, B, K, REC), i32(1, B), f32(2, B, K_kp, REC), i32(3, B),
+                               i32(4, B, K, self.max_slots), i32(5, B, K), i32(6, B, K_kp))
+
+    def _check(self, prediction):
+        B, C, C_kp, H, W, _, _ = self.shape
+        if prediction.keypoint_heatmap is None or prediction.keypoint_affinity is None:
+            raise ValueError("the prediction has no keypoint heads (keypoint_heatmap / keypoint_affinity are None)")
+        want = (("heatmap", prediction.heatmap, (B, C, H, W)), ("keypoint_heatmap", prediction.keypoint_heatmap,
+                                                                (B, C_kp, H, W)),
+                ("keypoint_affinity", prediction.keypoint_affinity, (B, C_kp, 2, H, W)),
+                ("size", prediction.size, (B, H, W, 2)), ("depth", prediction.depth, (B, H, W, 1)))
+        for name, t, shape in want:
+            if t is None and name == "depth":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                raise ValueError(f"{name} must be a float32 tensor")
+            if t.device != self.device:
+                raise ValueError(f"{name} is on {t.device}, the decoder on {self.device}")
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} shape {tuple(t.shape)} != decoder shape {shape}")
+
+    def __call__(self, prediction, model_config, score_threshold, keypoint_score_threshold) -> KeypointRecords:
+        """The three launches on the current stream; returns the device views. Refuses (ValueError, before
+        any launch) a prediction without keypoint heads, host tensors and shapes other than the decoder's."""
+        self._check(prediction)
+        mc = model_config
+        self.objects(prediction.heatmap, prediction.size, None, prediction.depth, 1, mc.downsample_ratio, mc.in_h,
+                     mc.in_w, score_threshold)
+        self.keypoints(prediction.keypoint_heatmap, prediction.size, None, None, 1, mc.downsample_ratio, mc.in_h,
+                       mc.in_w, keypoint_score_threshold, prediction.keypoint_affinity)
+        return self.match()
+
+    def match(self) -> KeypointRecords:
+        """The matching alone, on the records and counts the buffers hold (the last launch of a call)."""
+        B, _, C_kp, _, _, K, K_kp = self.shape
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        _lib.check(_lib.lib().tv_match_keypoints(
+            vp(self.records), vp(self.counts), vp(self.keypoint_records), vp(self.keypoint_counts),
+            vp(self.owner_label), vp(self.owner_slot), C_kp, self.max_slots, B, K, K_kp, vp(self.kp_det),
+            vp(self.slot_kp), vp(self.n_matched), _lib.stream_of(self.device)), "match_keypoints")
+        return KeypointRecords(self.records, self.counts, self.keypoint_records, self.keypoint_counts, self.slot_kp,
+                               self.n_matched, self.kp_det)
+
+    def host(self) -> KeypointRecords:
+        """The last call's arrays on the host: `packed` copied to pinned memory, one synchronisation. The
+        tensors are views of the decoder's pinned mirror, overwritten by the next host()."""
+        if self._host is None:
+            self._host = torch.empty(self.packed.numel(), dtype=torch.uint8, pin_memory=True)
+        with torch.cuda.device(self.device):
+            self._host.copy_(self.packed, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+        return self._views(self._host)
+
+
+_KP_DECODERS = {}  # (device, shape, owner tables) -> DeviceKeypointDecoder; under _DECODERS_LOCK
+
+
+def decode_keypoints_records(prediction, model_config, object_config, n_detections: int,
+                             keypoint_n_detections: int, score_threshold: float,
+                             keypoint_score_threshold: float) -> KeypointRecords:
+    """decode_keypoints() with the matching on the device and without the per-detection Python objects
+    (the keypoint analogue of decode_records): KeypointRecords of host numpy arrays — three launches, one
+    D2H copy, one host synchronisation. The prediction must be on the GPU."""
+    owner_label, owner_slot, _ = keypoint_owner_tables(object_config)
+    heat = prediction.heatmap
+    if not isinstance(heat, torch.Tensor) or not heat.is_cuda:
+        raise ValueError("the prediction must be on the GPU")
+    if prediction.keypoint_heatmap is None or prediction.keypoint_affinity is None:
+        raise ValueError("the prediction has no keypoint heads (keypoint_heatmap / keypoint_affinity are None)")
+    B, C, H, W = heat.shape
+    _empty_batch_check(B)
+    C_kp = prediction.keypoint_heatmap.shape[1]
+    key = (heat.device.index, B, C, C_kp, H, W, int(n_detections), int(keypoint_n_detections), tuple(owner_label),
+           tuple(owner_slot))
+    with _DECODERS_LOCK:
+        dec = _KP_DECODERS.get(key)
+        if dec is None:
+            if len(_KP_DECODERS) >= _DECODERS_MAX:
+                _KP_DECODERS.pop(next(iter(_KP_DECODERS)))
+            dec = DeviceKeypointDecoder(B, C, C_kp, H, W, int(n_detections), int(keypoint_n_detections), object_config,
+                                        heat.device)
+            _KP_DECODERS[key] = dec
+        with torch.cuda.device(heat.device):
+            dec(prediction, model_config, score_threshold, keypoint_score_threshold)
+            return KeypointRecords(*[t.numpy().copy() for t in dec.host()])
+
+
+def keypoint_detections_from_records(records, counts, keypoint_records, slot_kp, has_depth, model_config,
+                                     object_config, M_projection) -> List[List[KeypointDetection]]:
+    """The [[KeypointDetection]] of decode_keypoints() from KeypointRecords' host arrays (numpy or host
+    tensors), then the host PnP (_solve_poses) as there."""
+    records, counts, keypoint_records, slot_kp = (np.asarray(a) for a in (records, counts, keypoint_records, slot_kp))
+    out = []
+    for b in range(records.shape[0]):
+        dets = []
+        for d, r in enumerate(records[b, :counts[b]]):
+            label = int(r[0])
+            nk = len(object_config.configs[label].keypoints or [])
+            kps = [keypoint_records[b, k] if k >= 0 else None for k in slot_kp[b, d, :nk]]
+            dets.append(KeypointDetection(
+                label=label, score=float(r[1]), y=float(r[2]), x=float(r[3]), h=float(r[4]), w=float(r[5]),
+                depth=float(r[6]) if has_depth else None,
+                keypoints=[None if q is None else (float(q[2]), float(q[3])) for q in kps],
+                keypoint_scores=[None if q is None else float(q[1]) for q in kps],
+                keypoint_affinities=[None if q is None else (float(q[8]), float(q[9])) for q in kps],
+                cam_t_object=None))
         _solve_poses(dets, model_config, object_config, M_projection)
         out.append(dets)
     return out
