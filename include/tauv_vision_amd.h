@@ -454,6 +454,84 @@ int tv_train_keypoint_targets(const uint8_t* keypoint_valid, const int64_t* keyp
                               int32_t in_w, int32_t downsample_ratio, double heatmap_sigma, double affinity_sigma,
                               float* heatmap, float* affinity_weight, float* affinity, void* stream);
 
+/* The CenterNet training loss (loss.py:178-390) with its gradients, in three launches on `stream`:
+ * dense, objects, finalize, in that order. Device pointers; fp32 arithmetic; no host synchronisation;
+ * no float atomics and no waiting between workgroups, so two calls on the same inputs give the same bits.
+ *
+ * One description serves the three calls. tensor[i] is prediction tensor i (TV_LOSS_*): `data` in
+ * `dtype` (TV_F32 / TV_F16 / TV_BF16, the same for all) with element strides `stride`, and `grad`, a
+ * buffer of the same dtype and shape with element strides `grad_stride` that receives the gradient.
+ * The stride order is [b, c, y, x] for the heatmaps ([B, n_labels | n_keypoints, H, W]),
+ * [b, k, 2, y, x] for the affinity and [b, y, x, c] for the object heads ([B, H, W, 2 | 4 | 1]); any
+ * non-negative strides are taken (NCHW-contiguous, NHWC views, channel slices), nothing is copied.
+ * data == NULL: the head is absent (heatmap, size and offset must be present; the affinity needs the
+ * keypoint heatmap; an angle's bin and offset go together). grad == NULL for every tensor: values only.
+ * H = in_h / downsample_ratio, W = in_w / downsample_ratio. Truth: valid u8 [B, n_objects], label int64
+ * in [0, n_labels), center / size fp32 [B, n_objects, 2], roll / pitch / yaw / depth fp32
+ * [B, n_objects] (needed where the head is present), the keypoint instances as in
+ * tv_train_keypoint_targets (needed with the keypoint heatmap). angle_range: fp32 [3, n_labels], the
+ * modulo of roll, pitch, yaw per label (0 where the label has none: a NaN term, as in the reference).
+ * bins: angle_get_bins(angle_bin_overlap) as (center, min, max) of bin 0 and bin 1.
+ *
+ * tv_centernet_loss_dense: every cell of every heatmap plane once. The cell's target is computed as
+ *   tv_train_heatmap / tv_train_keypoint_targets compute it (sigma clamped to 0.1 for the object
+ *   heatmap only) and never stored. Focal terms (loss.py:302-317): p = sigmoid(z), positive where
+ *   isclose(target, 1), log(clamp(., 1e-4)) with the clamp's gradient 0 below the bound; affinity:
+ *   weight * (pred - target)^2. Writes d(-(loss_p + loss_n)) / dz and 2 weight (pred - target), not
+ *   yet scaled, to the gradients, zero-fills the object heads' gradients, and stores each workgroup's
+ *   sums (positive, negative, squared error, positive count) to `workspace`. 8- or 16-byte vector
+ *   accesses where all dense tensors and gradients are contiguous in (y, x) and aligned to four
+ *   elements. focal alpha, beta >= 1 (below 1 the reference's 0 * inf at saturated cells is not kept).
+ * tv_centernet_loss_objects: one thread per sample walks its objects in order: gathers every object
+ *   head at out_index_for_position(center), forms the size / offset L1, angle_loss and depth_loss
+ *   terms and stores their gradients, already scaled by lambda / n_valid with
+ *   n_valid = min(valid count, 1) (angles: times the valid count, over all objects, as the reference
+ *   has it), over the zero-filled gradients; the gradients of objects that share a cell are summed in
+ *   fp32 in object order and stored once. Must follow tv_centernet_loss_dense on the stream. Per-sample sums go to `workspace`.
+ * tv_centernet_loss_finalize: one workgroup sums the partial sums in a fixed order and writes
+ *   out[0..15]: total (= heatmap + every other term, added in the reference's order), keypoint_heatmap,
+ *   keypoint_affinity, offset, size, roll, pitch, yaw, depth, avg_size_error, max_size_error, the
+ *   heatmap term alone, N of the heatmap, N of the keypoint heatmap, the valid count, 0;
+ *   out[16..31]: the factor that scales tensor i's stored gradient (1 / N or 0 when N == 0 for the
+ *   heatmap, lambda / N for the keypoint heatmap, lambda for the affinity, 1 for the object heads).
+ * TV_EINVAL before any launch: null desc / workspace / out, a null pointer for a present head's truth,
+ * B < 1, an empty map, negative strides, a missing required head, an unknown dtype, or a workspace
+ * smaller than tv_centernet_loss_workspace_size. */
+enum { TV_LOSS_HEATMAP = 0, TV_LOSS_KEYPOINT_HEATMAP, TV_LOSS_KEYPOINT_AFFINITY, TV_LOSS_SIZE, TV_LOSS_OFFSET,
+       TV_LOSS_ROLL_BIN, TV_LOSS_ROLL_OFFSET, TV_LOSS_PITCH_BIN, TV_LOSS_PITCH_OFFSET, TV_LOSS_YAW_BIN,
+       TV_LOSS_YAW_OFFSET, TV_LOSS_DEPTH, TV_LOSS_TENSORS };
+typedef struct tv_loss_tensor {
+  const void* data;
+  void* grad;
+  int64_t stride[5];
+  int64_t grad_stride[5];
+} tv_loss_tensor;
+typedef struct tv_loss_desc {
+  int32_t dtype, B, n_objects, n_instances, n_labels, n_keypoints, in_h, in_w, downsample_ratio;
+  double keypoint_heatmap_sigma, keypoint_affinity_sigma, focal_alpha, focal_beta;
+  double lambda_keypoint_heatmap, lambda_keypoint_affinity, lambda_size, lambda_offset, lambda_angle, lambda_depth;
+  double bins[2][3];
+  tv_loss_tensor tensor[TV_LOSS_TENSORS];
+  const uint8_t* valid;
+  const int64_t* label;
+  const float *center, *size, *roll, *pitch, *yaw, *depth;
+  const uint8_t* keypoint_valid;
+  const int64_t *keypoint_label, *keypoint_object_index;
+  const float* keypoint_center;
+  const float* angle_range;
+} tv_loss_desc;
+int tv_centernet_loss_workspace_size(const tv_loss_desc* desc, int64_t* bytes);
+int tv_centernet_loss_dense(const tv_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream);
+int tv_centernet_loss_objects(const tv_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream);
+int tv_centernet_loss_finalize(const tv_loss_desc* desc, const void* workspace, int64_t workspace_bytes, float* out,
+                               void* stream);
+/* The backward pass of the loss: grad[i] *= *scale for the n elements of one dense gradient buffer of `dtype`
+ * that tv_centernet_loss_dense / _objects wrote (16-byte aligned). `scale` is a device fp32 scalar
+ * ((gradient of total + gradient of the tensor's term) * the tensor's factor from out[16..]); the product
+ * is formed in fp32 and rounded once. One pass, no recomputation. TV_EINVAL: null or misaligned pointers,
+ * n < 0, an unknown dtype. */
+int tv_centernet_loss_scale(void* grad, int32_t dtype, int64_t n, const float* scale, void* stream);
+
 /* Diagnostics (GPU tests): one DeformConv2d(x, offset, sigmoid(mask)) (DeformConv.forward,
  * centerpoint_dla.py:389-391: 3x3, stride 1, pad 1) + bias + activation (0 none, 1 ReLU, 2 leaky)
  * through the kernel the engine uses for DLA-34's DeformConv layers. x: compute-dtype NHWC

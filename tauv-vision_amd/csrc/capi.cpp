@@ -619,4 +619,32 @@ int tv_train_keypoint_targets(const uint8_t* keypoint_valid, const int64_t* keyp
   })
 }
 
+int tv_centernet_loss_workspace_size(const tv_loss_desc* desc, int64_t* bytes) {
+  TV_GUARD({
+    long long n = 0;
+    const int rc = tv::centernet_loss_workspace_size(desc, bytes ? &n : nullptr);
+    if (rc == TV_OK) *bytes = n;
+    return rc;
+  })
+}
+
+int tv_centernet_loss_dense(const tv_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream) {
+  TV_GUARD({ return tv::launch_centernet_loss_dense(desc, workspace, workspace_bytes, (hipStream_t)stream); })
+}
+
+int tv_centernet_loss_objects(const tv_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream) {
+  TV_GUARD({ return tv::launch_centernet_loss_objects(desc, workspace, workspace_bytes, (hipStream_t)stream); })
+}
+
+int tv_centernet_loss_finalize(const tv_loss_desc* desc, const void* workspace, int64_t workspace_bytes, float* out,
+                               void* stream) {
+  TV_GUARD({
+    return tv::launch_centernet_loss_finalize(desc, workspace, workspace_bytes, out, (hipStream_t)stream);
+  })
+}
+
+int tv_centernet_loss_scale(void* grad, int32_t dtype, int64_t n, const float* scale, void* stream) {
+  TV_GUARD({ return tv::launch_centernet_loss_scale(grad, dtype, n, scale, (hipStream_t)stream); })
+}
+
 }  // extern "C"

@@ -248,6 +248,17 @@ int launch_train_heatmap(const uint8_t* valid, const long long* label, const flo
 int launch_train_keypoints(const uint8_t* kvalid, const long long* klabel, const float* kcenter, const long long* kobj,
                            const float* center, int B, int n_inst, int n_obj, int K, int in_h, int in_w, int ratio,
                            double heat_sigma, double aff_sigma, float* heat, float* aw, float* aff, hipStream_t s);
+}  // namespace tv
+struct tv_loss_desc;
+namespace tv {
+// loss.hip: the CenterNet loss with its gradients (loss.py:178-390); the contracts are
+// tv_centernet_loss_*' in include/tauv_vision_amd.h. Arguments are checked here (return 1 = TV_EINVAL).
+int centernet_loss_workspace_size(const tv_loss_desc* d, long long* bytes);
+int launch_centernet_loss_dense(const tv_loss_desc* d, void* ws, long long ws_bytes, hipStream_t s);
+int launch_centernet_loss_objects(const tv_loss_desc* d, void* ws, long long ws_bytes, hipStream_t s);
+int launch_centernet_loss_finalize(const tv_loss_desc* d, const void* ws, long long ws_bytes, float* out,
+                                   hipStream_t s);
+int launch_centernet_loss_scale(void* grad, int dtype, long long n, const float* scale, hipStream_t s);
 // diag.cpp: one DeformConv2d + bias + activation through a chosen DCN kernel (GPU tests)
 int diag_dcn_conv(const void* x, const void* om, int B, int H, int W, int C, int om_ldc, const float* weight,
                   const float* bias, int N, int act, int dtype, int variant, void* out, hipStream_t s);

@@ -15,86 +15,37 @@
 // reference's exp is torch's CPU expf; this is the device expf (both ~1 ulp). The affinity's
 // sqrt and quotient are correctly rounded here; torch's CPU sqrt (MKL VML vsSqrt) returns one
 // ulp below the correctly rounded root for ~0.6% of fp32 inputs (tests/test_targets.py).
-#include "common.h"
-
-#include <cfloat>
-#include <cmath>
+// The per-cell functions live in targets_dev.h, which the loss kernels (loss.hip) share.
+#include "targets_dev.h"
 
 namespace tv {
 namespace targets {
 
-__device__ __forceinline__ float maximum_nan(float a, float b) {  // torch.maximum
-  return (a != a || b != b) ? __builtin_nanf("") : fmaxf(a, b);
-}
-__device__ __forceinline__ float nan_to_num(float v, float nan) {  // torch.nan_to_num(v, nan)
-  return v != v ? nan : v == INFINITY ? FLT_MAX : v == -INFINITY ? -FLT_MAX : v;
-}
-__device__ __forceinline__ int cell(float c, int in_size, int ratio) {
-  return (int)floorf(__fdiv_rn(__fmul_rn(c, (float)in_size), (float)ratio));
-}
-__device__ __forceinline__ float gauss(int x, int y, int cx, int cy, float den) {
-  const long long dx = (long long)x - cx, dy = (long long)y - cy;
-  const float d2 = (float)(dx * dx + dy * dy);
-  return expf(__fdiv_rn(-d2, den));
-}
-
 // heatmap [B][L][H][W]: grid (cells / 256, L, B)
-__global__ __launch_bounds__(256) void heatmap(const uint8_t* __restrict__ valid, const long long* __restrict__ label,
-                                                const float* __restrict__ center, int n_obj, int L, int in_h,
-                                                int in_w, int ratio, int H, int W, float den, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void heatmap(const Truth t, int L, float den, float* __restrict__ out) {
   const int q = blockIdx.x * 256 + threadIdx.x;
   const int l = blockIdx.y, b = blockIdx.z;
-  if (q >= H * W) return;
-  const int y = q / W, x = q - y * W;
-  float v = 0.f;
-  for (int o = 0; o < n_obj; ++o) {
-    const size_t bo = (size_t)b * n_obj + o;
-    if (!valid[bo] || label[bo] != l) continue;
-    const int cy = cell(center[2 * bo], in_h, ratio), cx = cell(center[2 * bo + 1], in_w, ratio);
-    v = maximum_nan(v, gauss(x, y, cx, cy, den));
-  }
-  out[((size_t)b * L + l) * H * W + q] = nan_to_num(v, 0.f);
+  if (q >= t.H * t.W) return;
+  const int y = q / t.W, x = q - y * t.W;
+  out[((size_t)b * L + l) * t.H * t.W + q] = heat_cell(t, b, l, y, x, den);
 }
 
 // keypoint heatmap / affinity weight [B][K][H][W], affinity [B][K][2][H][W]: grid (cells / 256, K, B)
-__global__ __launch_bounds__(256) void keypoints(const uint8_t* __restrict__ kvalid, const long long* __restrict__ klabel,
-                                                  const float* __restrict__ kcenter, const long long* __restrict__ kobj,
-                                                  const float* __restrict__ center, int n_inst, int n_obj, int K,
-                                                  int in_h, int in_w, int ratio, int H, int W, float den_h, float den_a,
+__global__ __launch_bounds__(256) void keypoints(const Truth t, int K, float den_h, float den_a,
                                                   float* __restrict__ heat, float* __restrict__ aw,
                                                   float* __restrict__ aff) {
   const int q = blockIdx.x * 256 + threadIdx.x;
   const int k = blockIdx.y, b = blockIdx.z;
+  const int H = t.H, W = t.W;
   if (q >= H * W) return;
   const int y = q / W, x = q - y * W;
-  // the cell's normalised position, as torch.stack((y / out_h, x / out_w)) forms it
-  const float py = __fdiv_rn((float)y, (float)H), px = __fdiv_rn((float)x, (float)W);
-  float vh = 0.f, va = 0.f, a0 = 0.f, a1 = 0.f, dist = INFINITY;
-  for (int i = 0; i < n_inst; ++i) {
-    const size_t bi = (size_t)b * n_inst + i;
-    if (!kvalid[bi] || klabel[bi] != k) continue;
-    const int cy = cell(kcenter[2 * bi], in_h, ratio), cx = cell(kcenter[2 * bi + 1], in_w, ratio);
-    vh = maximum_nan(vh, gauss(x, y, cx, cy, den_h));
-    va = maximum_nan(va, gauss(x, y, cx, cy, den_a));
-    const size_t bo = (size_t)b * n_obj + (size_t)kobj[bi];
-    const float d0 = nan_to_num(__fsub_rn(py, center[2 * bo]), 0.f);
-    const float d1 = nan_to_num(__fsub_rn(px, center[2 * bo + 1]), 0.f);
-    const float dd = nan_to_num(__fsqrt_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1))), 1.f);
-    if (dd < dist) {
-      a0 = __fdiv_rn(d0, dd);
-      a1 = __fdiv_rn(d1, dd);
-    }
-    dist = fminf(dist, dd);  // dd is never NaN here
-  }
+  const KeypointCell c = keypoint_cell(t, b, k, y, x, den_h, den_a);
   const size_t plane = (size_t)b * K + k;
-  heat[plane * H * W + q] = nan_to_num(vh, 0.f);
-  aw[plane * H * W + q] = nan_to_num(va, 0.f);
-  aff[(2 * plane) * H * W + q] = nan_to_num(a0, 0.f);
-  aff[(2 * plane + 1) * H * W + q] = nan_to_num(a1, 0.f);
+  heat[plane * H * W + q] = c.heat;
+  aw[plane * H * W + q] = c.weight;
+  aff[(2 * plane) * H * W + q] = c.a0;
+  aff[(2 * plane + 1) * H * W + q] = c.a1;
 }
-
-// fl32(2 sigma^2) with sigma^2 in double, as the Python expression `2 * sigma ** 2` hands it to torch
-float den_of(double sigma) { return (float)(2.0 * (sigma * sigma)); }
 
 }  // namespace targets
 
@@ -110,8 +61,11 @@ int launch_train_heatmap(const uint8_t* valid, const long long* label, const flo
     return 2;
   }
   if (sigma < 0.1) sigma = 0.1;  // loss.py:59-63
-  hipLaunchKernelGGL(targets::heatmap, dim3((H * W + 255) / 256, L, B), dim3(256), 0, s, valid, label, center, n_obj, L,
-                     in_h, in_w, ratio, H, W, targets::den_of(sigma), out);
+  targets::Truth t{};
+  t.valid = valid; t.label = label; t.center = center; t.n_obj = n_obj;
+  t.in_h = in_h; t.in_w = in_w; t.ratio = ratio; t.H = H; t.W = W;
+  hipLaunchKernelGGL(targets::heatmap, dim3((H * W + 255) / 256, L, B), dim3(256), 0, s, t, L, targets::den_of(sigma),
+                     out);
   TV_HIP(hipGetLastError());
   return 0;
 }
@@ -129,9 +83,12 @@ int launch_train_keypoints(const uint8_t* kvalid, const long long* klabel, const
     set_error("generate_keypoint_heatmap: empty output map");
     return 2;
   }
-  hipLaunchKernelGGL(targets::keypoints, dim3((H * W + 255) / 256, K, B), dim3(256), 0, s, kvalid, klabel, kcenter, kobj,
-                     center, n_inst, n_obj, K, in_h, in_w, ratio, H, W, targets::den_of(heat_sigma),
-                     targets::den_of(aff_sigma), heat, aw, aff);
+  targets::Truth t{};
+  t.kvalid = kvalid; t.klabel = klabel; t.kcenter = kcenter; t.kobj = kobj; t.center = center;
+  t.n_inst = n_inst; t.n_obj = n_obj;
+  t.in_h = in_h; t.in_w = in_w; t.ratio = ratio; t.H = H; t.W = W;
+  hipLaunchKernelGGL(targets::keypoints, dim3((H * W + 255) / 256, K, B), dim3(256), 0, s, t, K,
+                     targets::den_of(heat_sigma), targets::den_of(aff_sigma), heat, aw, aff);
   TV_HIP(hipGetLastError());
   return 0;
 }

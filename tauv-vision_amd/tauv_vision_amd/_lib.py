@@ -29,6 +29,27 @@ class WeightView(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("data", c_vp), ("numel", c_i64)]
 
 
+LOSS_TENSORS = ("heatmap", "keypoint_heatmap", "keypoint_affinity", "size", "offset", "roll_bin", "roll_offset",
+                "pitch_bin", "pitch_offset", "yaw_bin", "yaw_offset", "depth")  # TV_LOSS_*
+
+
+class LossTensor(ctypes.Structure):
+    _fields_ = [("data", c_vp), ("grad", c_vp), ("stride", c_i64 * 5), ("grad_stride", c_i64 * 5)]
+
+
+class LossDesc(ctypes.Structure):
+    """tv_loss_desc (include/tauv_vision_amd.h)."""
+    _fields_ = [(n, c_i32) for n in ("dtype", "B", "n_objects", "n_instances", "n_labels", "n_keypoints", "in_h",
+                                     "in_w", "downsample_ratio")] + \
+               [(n, c_f64) for n in ("keypoint_heatmap_sigma", "keypoint_affinity_sigma", "focal_alpha", "focal_beta",
+                                     "lambda_keypoint_heatmap", "lambda_keypoint_affinity", "lambda_size",
+                                     "lambda_offset", "lambda_angle", "lambda_depth")] + \
+               [("bins", (c_f64 * 3) * 2), ("tensor", LossTensor * len(LOSS_TENSORS))] + \
+               [(n, c_vp) for n in ("valid", "label", "center", "size", "roll", "pitch", "yaw", "depth",
+                                    "keypoint_valid", "keypoint_label", "keypoint_object_index", "keypoint_center",
+                                    "angle_range")]
+
+
 EXPORTS = {
     "tv_model_param_count": ([ctypes.POINTER(ModelDesc), ctypes.POINTER(c_i32)], c_i32),
     "tv_model_param_info": ([ctypes.POINTER(ModelDesc), c_i32, ctypes.c_char_p, c_i32, ctypes.POINTER(c_i64),
@@ -102,6 +123,11 @@ EXPORTS = {
     "tv_train_heatmap": ([c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_vp, c_vp], c_i32),
     "tv_train_keypoint_targets": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                    c_f64, c_f64, c_vp, c_vp, c_vp, c_vp], c_i32),
+    "tv_centernet_loss_workspace_size": ([ctypes.POINTER(LossDesc), ctypes.POINTER(c_i64)], c_i32),
+    "tv_centernet_loss_dense": ([ctypes.POINTER(LossDesc), c_vp, c_i64, c_vp], c_i32),
+    "tv_centernet_loss_objects": ([ctypes.POINTER(LossDesc), c_vp, c_i64, c_vp], c_i32),
+    "tv_centernet_loss_finalize": ([ctypes.POINTER(LossDesc), c_vp, c_i64, c_vp, c_vp], c_i32),
+    "tv_centernet_loss_scale": ([c_vp, c_i32, c_i64, c_vp, c_vp], c_i32),
     "tv_diag_dcn_conv": ([c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32,
                           c_vp, c_vp], c_i32),
     "tv_diag_conv_small": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
