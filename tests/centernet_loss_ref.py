@@ -7,8 +7,12 @@ gen_golden_loss.py from the reference itself); in float64 it is the yardstick th
 Besides each term it returns S, the sum of the absolute values of the elements the term sums (with the
 term's lambda and divisor applied): the scale of the tests' tolerances.
 
-Fixture helpers: `load_case(name)` rebuilds a fixture's configs, truth and prediction arrays.
+Case helpers: `load_case(name)` rebuilds a fixture's configs, truth and prediction arrays; `case_inputs`
+does the same for a fixture or a generated case (centernet_loss_cases.GENERATED, no stored results);
+`restated` runs the restatement in float64 and fp32 once per case; `check_values` / `check_grads` are the
+tolerance rule of the GPU tests (test_gpu_centernet_loss.py states it), in plain numpy.
 """
+import functools
 from math import pi
 from types import SimpleNamespace
 
@@ -16,11 +20,11 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import centernet_loss_cases as C
+from centernet_loss_cases import HEADS
 from helpers import golden
 from oracle import ref_targets as rt
 
-HEADS = ("heatmap", "keypoint_heatmap", "keypoint_affinity", "size", "offset", "roll_bin", "roll_offset", "pitch_bin",
-         "pitch_offset", "yaw_bin", "yaw_offset", "depth")
 TERMS = ("total", "heatmap", "keypoint_heatmap", "keypoint_affinity", "offset", "size", "roll", "pitch", "yaw", "depth",
          "avg_size_error", "max_size_error")
 CASES = ("loss_allheads_b2_24x40", "loss_torpedo_b3_23x40", "loss_tiny_b1_5x7", "loss_allheads_b2_24x40_novalid",
@@ -190,19 +194,12 @@ def load_case(name):
     reference's shapes (absent heads None)."""
     g, base = golden(name), golden(base_name(name))
     t = lambda k: torch.from_numpy(base[k])  # noqa: E731
-    ds = int(base["downsamples"])
-    r = 1 << ds
-    mc = SimpleNamespace(in_h=int(base["in_h"]), in_w=int(base["in_w"]), downsamples=ds, downsample_ratio=r,
-                         out_h=int(base["in_h"]) // r, out_w=int(base["in_w"]) // r,
-                         angle_bin_overlap=float(base["angle_bin_overlap"]))
-    tc = SimpleNamespace(**{k[3:]: float(base[k]) for k in base.files if k.startswith("tc_")})
-    moduli = base["moduli"]  # [3, n_labels] roll, pitch, yaw; NaN: None
-    cfgs = [SimpleNamespace(**{axis: SimpleNamespace(modulo=None if np.isnan(moduli[a, l]) else float(moduli[a, l]))
-                               for a, axis in enumerate(("roll", "pitch", "yaw"))}) for l in range(moduli.shape[1])]
-    oc = SimpleNamespace(n_labels=int(base["n_labels"]), n_keypoints=int(base["n_keypoints"]), configs=cfgs)
-    truth = SimpleNamespace(**{k: t(k) for k in ("valid", "label", "center", "size", "roll", "pitch", "yaw", "depth",
-                                                 "keypoint_valid", "keypoint_label", "keypoint_center",
-                                                 "keypoint_object_index")})
+    mc, tc, oc = C.namespaces(int(base["in_h"]), int(base["in_w"]), int(base["downsamples"]),
+                              float(base["angle_bin_overlap"]),
+                              {k[3:]: float(base[k]) for k in base.files if k.startswith("tc_")},
+                              base["moduli"], int(base["n_keypoints"]))
+    assert oc.n_labels == int(base["n_labels"])
+    truth = SimpleNamespace(**{k: t(k) for k in C.TRUTH})
     if name.endswith("_novalid"):
         truth.valid = torch.zeros_like(truth.valid)
     if name.endswith("_nopositive"):
@@ -215,3 +212,74 @@ def leaves(pred, dtype):
     """The prediction dict as a namespace of leaf tensors of `dtype` that require grad."""
     return SimpleNamespace(**{h: None if v is None else v.to(dtype).clone().requires_grad_(True)
                               for h, v in pred.items()})
+
+
+def case_inputs(name):
+    """-> (g, mc, tc, oc, truth, pred) of a fixture (load_case) or of a generated case (g None)."""
+    if name in C.GENERATED:
+        return (None,) + C.make_case(C.GENERATED[name])
+    return load_case(name)
+
+
+def _numpy(d):
+    return {k: v.detach().double().cpu().numpy() for k, v in d.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def restated(name, rounding=torch.float32):
+    """(values64, S, grads64, values32, grads32) of a case, the prediction rounded to `rounding` first. The
+    fp32 side of a fixture in fp32 is the reference's own stored results, else the fp32 restatement. The
+    results are shared between the tests: they are not to be modified."""
+    g, mc, tc, oc, truth, pred = case_inputs(name)
+    pred = {h: None if v is None else v.to(rounding).float() for h, v in pred.items()}
+    out = []
+    for dtype in (torch.float64, torch.float32):
+        p = leaves(pred, dtype)
+        terms, S = loss_ref(p, truth, mc, tc, oc, dtype)
+        terms["total"].backward()
+        out += [_numpy(terms), S, {h: getattr(p, h).grad.double().numpy() for h in HEADS if pred[h] is not None}]
+    v64, S, g64, v32, _, g32 = out
+    if g is not None and rounding == torch.float32:  # the reference's own fp32 results
+        v32 = {t: g["val_" + t].astype(np.float64) for t in TERMS if "val_" + t in g.files}
+        g32 = {h: g["grad_" + h].astype(np.float64) for h in g64}
+    return v64, S, g64, v32, g32
+
+
+FLOOR = 2.0 ** -20
+
+
+def check_values(dev, v64, S, v32):
+    """-> the worst error over its tolerance."""
+    worst = 0.0
+    for t, want in v64.items():
+        if t == "heatmap_alone":
+            continue
+        if np.isnan(want) or np.isnan(v32[t]):
+            assert np.isnan(want) and np.isnan(v32[t]) and np.isnan(dev[t]), t
+            continue
+        e_ref = abs(v32[t] - want) / S[t] if S[t] else 0.0
+        tol = max(4 * e_ref, FLOOR) * S[t]
+        print(f"{t}: dev {dev[t]:.9g} f64 {want:.9g} err {abs(dev[t] - want):.3g} tol {tol:.3g} e_ref {e_ref:.3g}")
+        assert abs(dev[t] - want) <= tol, (t, dev[t], want, tol)
+        if tol:
+            worst = max(worst, float(abs(dev[t] - want) / tol))
+    return worst
+
+
+def check_grads(dev, g64, g32, half=0.0):
+    """-> the worst error over its bound."""
+    worst = 0.0
+    for h, want in g64.items():
+        nan = np.isnan(want)
+        np.testing.assert_array_equal(np.isnan(g32[h]), nan, err_msg=h)
+        np.testing.assert_array_equal(np.isnan(dev[h]), nan, err_msg=h)
+        w, d, r = want[~nan], dev[h][~nan], g32[h][~nan]
+        if w.size == 0:
+            continue
+        bound = max(4 * np.abs(r - w).max(), FLOOR * np.abs(w).max())
+        err = np.abs(d - w)
+        print(f"grad {h}: max err {err.max():.3g} bound {bound:.3g} max |g64| {np.abs(w).max():.3g}")
+        assert (err <= bound + half * np.abs(w)).all(), (h, float((err - half * np.abs(w)).max()), bound)
+        if bound:
+            worst = max(worst, float((err / (bound + half * np.abs(w))).max()))
+    return worst

@@ -1,5 +1,10 @@
 """tauv_vision_amd.loss.loss (csrc/loss.hip) on the GPU against the float64 restatement of the reference's
-loss (tests/centernet_loss_ref.py) on the fixtures the reference itself produced (tests/golden/loss_*.npz).
+loss (tests/centernet_loss_ref.py): on the fixtures the reference itself produced (tests/golden/loss_*.npz),
+whose maps fit one dense workgroup per plane, and on the generated cases of tests/centernet_loss_cases.py
+(rows, vec3, scal3, many), which reach the launcher's other schedules: vectors that straddle rows, three
+workgroups per plane with a partly live last one on either route, 260 samples, half dtypes on the scalar
+route and through NHWC slices, a misaligned heatmap. Each of those runs asserts the route it took, through
+the workgroups per plane that the workspace size of the call's own description implies.
 
 Tolerances (none fixed in advance; S and the restatement are described in centernet_loss_ref.py):
   values     |T_dev - T64| <= max(4 e_ref, 2^-20) S with e_ref = |T_ref - T64| / S the reference's own fp32
@@ -10,7 +15,17 @@ Tolerances (none fixed in advance; S and the restatement are described in center
              inputs plus 2^-10 |g64| / 2^-7 |g64| per element, the rounding of the stored gradient.
 NaN is required exactly where the reference has NaN. With half inputs the restatement runs on the
 half-rounded prediction, and the fp32 side of e_ref is the fp32 restatement on that same prediction
-(test_centernet_loss_ref_cpu.py shows it equals the reference bit for bit).
+(test_centernet_loss_ref_cpu.py shows it equals the reference bit for bit); so is the fp32 side of every
+generated case. The rule itself (check_values / check_grads) lives in centernet_loss_ref.py, where
+test_centernet_loss_cases_cpu.py shows that it reports a dropped workgroup, partials of the wrong kind, a
+vector written one row down, a dropped sample and an ungathered object.
+
+Measured on MI355X, generated cases (profiles/loss/generated_cases.json; worst value error over its
+tolerance / worst gradient error over its bound, 1 is the limit):
+  rows   fp32 0.10 / 0.25   fp16 0.25 / 0.91   bf16 0.19 / 0.89   misaligned fp32 0.10 / 0.25, fp16 0.25 / 0.91
+  vec3   fp32 0.25 / 0.28   fp16 NHWC slices 0.38 / 0.81
+  scal3  fp32 0.18 / 0.25   fp16 0.19 / 0.80   bf16 0.20 / 0.78
+  many   fp32 0.08 / 0.25
 """
 import ctypes
 import functools
@@ -21,40 +36,22 @@ import pytest
 import torch
 
 import centernet_loss_ref as R
+from centernet_loss_ref import FLOOR, _numpy, check_grads, check_values, restated  # noqa: F401
+from helpers import record_measurement
 
 pytestmark = pytest.mark.gpu
 
 A = "loss_allheads_b2_24x40"
 DENSE = ("heatmap", "keypoint_heatmap", "keypoint_affinity")
-FLOOR = 2.0 ** -20
 HALF = {torch.float16: 2.0 ** -10, torch.bfloat16: 2.0 ** -7}
+# generated case: the workgroups per plane (gx) of the route it is meant to run, of the scalar route
+GX = {"rows": (1, 3), "vec3": (3, 9), "scal3": (3, 3), "many": (1, 1)}
 
 
-def _numpy(d):
-    return {k: v.detach().double().cpu().numpy() for k, v in d.items()}
-
-
-@functools.lru_cache(maxsize=None)
-def restated(name, rounding=torch.float32):
-    """(values64, S, grads64, values32, grads32) of a fixture, the prediction rounded to `rounding` first."""
-    g, mc, tc, oc, truth, pred = R.load_case(name)
-    pred = {h: None if v is None else v.to(rounding).float() for h, v in pred.items()}
-    out = []
-    for dtype in (torch.float64, torch.float32):
-        p = R.leaves(pred, dtype)
-        terms, S = R.loss_ref(p, truth, mc, tc, oc, dtype)
-        terms["total"].backward()
-        out += [_numpy(terms), S, {h: getattr(p, h).grad.double().numpy() for h in R.HEADS if pred[h] is not None}]
-    v64, S, g64, v32, _, g32 = out
-    if rounding == torch.float32:  # the reference's own fp32 results
-        v32 = {t: g["val_" + t].astype(np.float64) for t in R.TERMS if "val_" + t in g.files}
-        g32 = {h: g["grad_" + h].astype(np.float64) for h in g64}
-    return v64, S, g64, v32, g32
-
-
-def reference_layout(pred, dtype, dev="cuda"):
+def reference_layout(pred, dtype, dev="cuda", heatmap_offset=0):
     """The reference torch model's layout: NCHW-contiguous heatmaps, NHWC views of NCHW heads.
-    -> (leaves, views): the leaves require grad."""
+    -> (leaves, views): the leaves require grad. With `heatmap_offset` the heatmap is a contiguous view that
+    many elements into a larger buffer (its gradient is retained on the view)."""
     leaf, view = {}, {}
     for h, v in pred.items():
         if v is None:
@@ -62,6 +59,12 @@ def reference_layout(pred, dtype, dev="cuda"):
             continue
         nchw = v if h in DENSE else v.permute(0, 3, 1, 2)
         leaf[h] = nchw.to(dev, dtype).contiguous().requires_grad_(True)
+        if h == "heatmap" and heatmap_offset:
+            buf = torch.zeros(v.numel() + 2 * heatmap_offset, dtype=dtype, device=dev)
+            buf[heatmap_offset:heatmap_offset + v.numel()] = leaf[h].detach().reshape(-1)
+            leaf[h] = buf.requires_grad_(True)[heatmap_offset:heatmap_offset + v.numel()].view(v.shape)
+            leaf[h].retain_grad()
+            assert leaf[h].is_contiguous() and leaf[h].data_ptr() % (4 * leaf[h].element_size())
         view[h] = leaf[h] if h in DENSE else leaf[h].permute(0, 2, 3, 1)
     return leaf, view
 
@@ -75,48 +78,82 @@ def cuda_truth(truth):
     return L.PoseSample(**{k: v.cuda() for k, v in vars(truth).items()})
 
 
+def nhwc_slices(pred, oc, dtype=torch.float32):
+    """The prediction as channel slices of one NHWC tensor (prediction_from_nhwc).
+    -> (base, views, the tauv_vision_amd object config, its channel table)."""
+    from tauv_vision_amd.centernet import prediction_fields, prediction_from_nhwc
+    toc = object_config_of(oc)
+    fields = prediction_fields(toc)
+    B, H, W = pred["size"].shape[:3]
+    base = torch.zeros((B, H, W, sum(n for _, n in fields.values())))
+    for h, (s, n) in fields.items():
+        v = pred[h]
+        v = v.permute(0, 2, 3, 1) if h in DENSE[:2] else v.permute(0, 3, 4, 1, 2).reshape(B, H, W, n) \
+            if h == "keypoint_affinity" else v
+        base[..., s:s + n] = v
+    base = base.to("cuda", dtype).requires_grad_(True)
+    return base, prediction_from_nhwc(base, toc), toc, fields
+
+
+def workgroups_per_plane(desc):
+    """gx of a call's description, from the workspace the library asks for:
+    bytes = 4 * (4 * B * (L + K) * gx + 16 * B)."""
+    from tauv_vision_amd import _lib
+    n = ctypes.c_int64()
+    assert _lib.lib().tv_centernet_loss_workspace_size(ctypes.byref(desc), ctypes.byref(n)) == _lib.TV_OK
+    B = desc.B
+    P = desc.n_labels + (desc.n_keypoints if desc.tensor[_lib.LOSS_TENSORS.index("keypoint_heatmap")].data else 0)
+    floats = n.value // 4 - 16 * B
+    assert n.value % 4 == 0 and floats > 0 and floats % (4 * B * P) == 0, (n.value, B, P)
+    return floats // (4 * B * P)
+
+
 @functools.lru_cache(maxsize=None)
-def device(name, dtype=torch.float32):
-    """(values, grads) of loss() on a fixture in the reference's layout, as float64 numpy."""
+def launched(name, dtype=torch.float32, layout="reference"):
+    """(values, grads, gx) of one loss() call and its backward on a case, as float64 numpy; gx the dense
+    workgroups per plane of the description the call handed the library. Layouts: "reference" (the
+    reference model's), "misaligned" (the same with the heatmap four bytes into a larger buffer), "nhwc"
+    (channel slices of one NHWC tensor; the gradients are those the loss returns for the slices)."""
     from tauv_vision_amd import loss as L
-    g, mc, tc, oc, truth, pred = R.load_case(name)
-    leaf, view = reference_layout(pred, dtype)
-    losses = L.loss(SimpleNamespace(**view), cuda_truth(truth), mc, tc, oc, None)
+    g, mc, tc, oc, truth, pred = R.case_inputs(name)
+    gx, run = [], L._Call.run
+
+    def spy(self, tensors, want):
+        out = run(self, tensors, want)
+        gx.append(workgroups_per_plane(self.desc))  # while the tensors the description points to are alive
+        return out
+    seen = {}
+    if layout == "nhwc":
+        base, views, oc, _ = nhwc_slices(pred, oc, dtype)
+        for h in R.HEADS:
+            assert not getattr(views, h).is_contiguous()
+            getattr(views, h).register_hook(lambda gr, h=h: seen.__setitem__(h, gr))
+    else:
+        leaf, view = reference_layout(pred, dtype, heatmap_offset=4 // dtype.itemsize if layout == "misaligned" else 0)
+        views = SimpleNamespace(**view)
+    L._Call.run = spy
+    try:
+        losses = L.loss(views, cuda_truth(truth), mc, tc, oc, None)
+    finally:
+        L._Call.run = run
     assert losses.heatmap is losses.total
     losses.total.backward()
     vals = {t: getattr(losses, t) for t in R.TERMS}
+    present = [t for t in R.TERMS if "val_" + t in g.files] if g is not None else \
+        [t for t in R.TERMS if t in restated(name)[0]]
     for t, v in vals.items():
-        assert (v.dim() == 0 and v.is_cuda and v.dtype == torch.float32) == ("val_" + t in g.files), t
-    for h, t in leaf.items():
-        assert t.grad.dtype == dtype and t.grad.shape == t.shape, h
-    return _numpy({t: v for t, v in vals.items() if v.dim() == 0}), _numpy(leaf_grads(leaf))
+        assert (v.dim() == 0 and v.is_cuda and v.dtype == torch.float32) == (t in present), t
+    if layout != "nhwc":
+        for h, t in leaf.items():
+            assert t.grad.dtype == dtype and t.grad.shape == t.shape, h
+        seen = leaf_grads(leaf)
+    assert len(gx) == 1
+    return _numpy({t: v for t, v in vals.items() if v.dim() == 0}), _numpy(seen), gx[0]
 
 
-def check_values(dev, v64, S, v32):
-    for t, want in v64.items():
-        if t == "heatmap_alone":
-            continue
-        if np.isnan(want) or np.isnan(v32[t]):
-            assert np.isnan(want) and np.isnan(v32[t]) and np.isnan(dev[t]), t
-            continue
-        e_ref = abs(v32[t] - want) / S[t] if S[t] else 0.0
-        tol = max(4 * e_ref, FLOOR) * S[t]
-        print(f"{t}: dev {dev[t]:.9g} f64 {want:.9g} err {abs(dev[t] - want):.3g} tol {tol:.3g} e_ref {e_ref:.3g}")
-        assert abs(dev[t] - want) <= tol, (t, dev[t], want, tol)
-
-
-def check_grads(dev, g64, g32, half=0.0):
-    for h, want in g64.items():
-        nan = np.isnan(want)
-        np.testing.assert_array_equal(np.isnan(g32[h]), nan, err_msg=h)
-        np.testing.assert_array_equal(np.isnan(dev[h]), nan, err_msg=h)
-        w, d, r = want[~nan], dev[h][~nan], g32[h][~nan]
-        if w.size == 0:
-            continue
-        bound = max(4 * np.abs(r - w).max(), FLOOR * np.abs(w).max())
-        err = np.abs(d - w)
-        print(f"grad {h}: max err {err.max():.3g} bound {bound:.3g} max |g64| {np.abs(w).max():.3g}")
-        assert (err <= bound + half * np.abs(w)).all(), (h, float((err - half * np.abs(w)).max()), bound)
+def device(name, dtype=torch.float32):
+    """(values, grads) of loss() on a case in the reference's layout, as float64 numpy."""
+    return launched(name, dtype)[:2]
 
 
 @pytest.mark.parametrize("name", R.CASES)
@@ -141,6 +178,53 @@ def test_half_inputs(dtype):
     check_grads(grads, g64, g32, HALF[dtype])
 
 
+def _measured(name, dtype, layout, vals, grads):
+    """Checks a generated case's run against the float64 restatement and records the worst ratios."""
+    v64, S, g64, v32, g32 = restated(name, dtype)
+    worst = {"values": check_values(vals, v64, S, v32), "gradients": check_grads(grads, g64, g32, HALF.get(dtype, 0.0))}
+    key = f"loss/{name}/{str(dtype)[len('torch.'):]}" + ("" if layout == "reference" else "/" + layout)
+    record_measurement(key, worst)
+    print(key, worst)
+
+
+@pytest.mark.parametrize("name,dtype", [("rows", torch.float32), ("rows", torch.float16), ("rows", torch.bfloat16),
+                                        ("vec3", torch.float32), ("scal3", torch.float32), ("scal3", torch.float16),
+                                        ("scal3", torch.bfloat16), ("many", torch.float32)],
+                         ids=lambda v: v if isinstance(v, str) else str(v)[len("torch."):])
+def test_generated_case(name, dtype):
+    """A generated case (centernet_loss_cases.GENERATED) in the reference's layout, on the route it was
+    made for: values and gradients against the float64 restatement."""
+    vals, grads, gx = launched(name, dtype)
+    assert gx == GX[name][0], (name, gx)
+    _measured(name, dtype, "reference", vals, grads)
+
+
+def test_generated_nhwc_slices_in_fp16():
+    """vec3 in fp16 as channel slices of one NHWC tensor: the scalar route through the slices' strides. The
+    per-cell arithmetic and the scale do not depend on the route: the gradients have the bits of the
+    contiguous run's (vector route, three workgroups per plane)."""
+    vals, grads, gx = launched("vec3", torch.float16, "nhwc")
+    _, want, gx_vec = launched("vec3", torch.float16)
+    assert (gx_vec, gx) == GX["vec3"]
+    assert sorted(grads) == sorted(want)
+    for h in want:
+        np.testing.assert_array_equal(grads[h], want[h], err_msg=h)
+    _measured("vec3", torch.float16, "nhwc", vals, grads)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16], ids=["fp32", "fp16"])
+def test_generated_misaligned_heatmap_leaves_the_vector_route(dtype):
+    """rows with the heatmap a contiguous view four bytes (one fp32, two fp16 elements) into a larger
+    buffer: vector_ok's alignment mask sends the call down the scalar route, and every gradient has the
+    aligned run's bits."""
+    vals, grads, gx = launched("rows", dtype, "misaligned")
+    _, want, gx_vec = launched("rows", dtype)
+    assert (gx_vec, gx) == GX["rows"]
+    for h in want:
+        np.testing.assert_array_equal(grads[h], want[h], err_msg=h)
+    _measured("rows", dtype, "misaligned", vals, grads)
+
+
 def object_config_of(oc):
     """A tauv_vision_amd ObjectConfigSet with the fixture's labels, angle moduli, depth and keypoint count."""
     import tauv_vision_amd as tv
@@ -159,19 +243,8 @@ def test_layouts_bit_equal_and_nothing_copied(monkeypatch):
     from tauv_vision_amd import _lib, loss as L
     calls, run = [], L._Call.run
     monkeypatch.setattr(L._Call, "run", lambda self, tensors, want: (calls.append(self), run(self, tensors, want))[1])
-    from tauv_vision_amd.centernet import prediction_fields, prediction_from_nhwc
     g, mc, tc, oc, truth, pred = R.load_case(A)
-    toc = object_config_of(oc)
-    fields = prediction_fields(toc)
-    B, H, W = pred["size"].shape[:3]
-    base = torch.zeros((B, H, W, sum(n for _, n in fields.values())))
-    for h, (s, n) in fields.items():
-        v = pred[h]
-        v = v.permute(0, 2, 3, 1) if h in DENSE[:2] else v.permute(0, 3, 4, 1, 2).reshape(B, H, W, n) \
-            if h == "keypoint_affinity" else v
-        base[..., s:s + n] = v
-    base = base.cuda().requires_grad_(True)
-    views = prediction_from_nhwc(base, toc)
+    base, views, toc, fields = nhwc_slices(pred, oc)
     kept = {h: getattr(views, h) for h in R.HEADS}
     seen = {}  # the gradient tensors as the loss returns them, before autograd folds them into base.grad
     for h, t in kept.items():
@@ -203,11 +276,9 @@ def test_layouts_bit_equal_and_nothing_copied(monkeypatch):
     assert leaf["size"].grad.stride() == leaf["size"].stride()
 
 
-def test_two_calls_bit_equal_on_dirty_buffers(monkeypatch):
-    """The second call gets every buffer it allocates (gradients, partial sums, outputs) prefilled with
-    0x5A: each byte it returns was written by the call."""
+def _second_call_on_dirty_buffers(monkeypatch, name):
     from tauv_vision_amd import loss as L
-    first = device(A)
+    first = device(name)
     empty, empty_like = torch.empty, torch.empty_like
 
     def dirty(make):
@@ -219,7 +290,7 @@ def test_two_calls_bit_equal_on_dirty_buffers(monkeypatch):
         return f
     monkeypatch.setattr(torch, "empty", dirty(empty))
     monkeypatch.setattr(torch, "empty_like", dirty(empty_like))
-    g, mc, tc, oc, truth, pred = R.load_case(A)
+    g, mc, tc, oc, truth, pred = R.case_inputs(name)
     leaf, view = reference_layout(pred, torch.float32)
     losses = L.loss(SimpleNamespace(**view), cuda_truth(truth), mc, tc, oc, None)
     losses.total.backward()
@@ -228,6 +299,17 @@ def test_two_calls_bit_equal_on_dirty_buffers(monkeypatch):
         assert float(getattr(losses, t).detach().double()) == v, t
     for h, v in _numpy(leaf_grads(leaf)).items():
         np.testing.assert_array_equal(v, first[1][h], err_msg=h)
+
+
+def test_two_calls_bit_equal_on_dirty_buffers(monkeypatch):
+    """The second call gets every buffer it allocates (gradients, partial sums, outputs) prefilled with
+    0x5A: each byte it returns was written by the call."""
+    _second_call_on_dirty_buffers(monkeypatch, A)
+
+
+def test_generated_two_calls_bit_equal_on_dirty_buffers(monkeypatch):
+    """The same on vec3: three workgroups per plane, the last one partly live."""
+    _second_call_on_dirty_buffers(monkeypatch, "vec3")
 
 
 def test_drop_in_conv_head():
