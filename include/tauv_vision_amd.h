@@ -576,6 +576,21 @@ int tv_diag_conv_burst(const void* const* src, const int32_t* geom, int32_t nseg
  * out[3] the LDS the layer's staging would need. */
 int tv_diag_burst_plan(const int32_t* geom, int32_t nseg, int32_t B, int32_t Ho, int32_t Wo, int32_t N, int32_t* out);
 
+/* Diagnostics (host only, no GPU needed): op `op` of the model's plan as tv_engine_create would
+ * upload it: BatchNorm folded, packed [Npad][Kpad] in the compute dtype. desc / weights as
+ * tv_engine_create, knobs as tv_engine_create_diag (NULL: none); the engine is configured for 256
+ * compute units. info = {ops in the plan, the op's kind, Npad, Kpad, its segment count} (info[0] is
+ * set even when `op` is out of range: TV_EINVAL); label: the op's label (NULL: skipped); segs[i], for
+ * the first seg_cap segments = {kernel height, kernel width (a row-expanded source: its taps per
+ * pixel), the source's stored channels, ci0, cin, k-steps}; size = the bytes of the weight, the fp32
+ * bias and the extra buffer: the convt3 fragments of a whole ConvTranspose2d, or the fused 1x1
+ * heads' fragments followed by their fp32 bias and the int32 head_row0[16], head_nrows[16]. A
+ * non-NULL weight / bias / extra is filled when its cap[] equals that size. An op without weights
+ * reports zeros. TV_ENOTFOUND: a state_dict key is missing or has the wrong element count. */
+int tv_diag_pack_op(const tv_model_desc* desc, const tv_weight_view* weights, int32_t n_weights, const char* knobs,
+                    int32_t op, int32_t info[5], char* label, int32_t label_cap, int32_t (*segs)[6], int32_t seg_cap,
+                    int64_t size[3], void* weight, void* bias, void* extra, const int64_t cap[3]);
+
 /* Diagnostics (GPU tests): one narrow-channel Conv2d(C, N, 3, stride, padding 1) + bias + activation
  * (DLA-34's full-resolution base levels, centerpoint_dla.py:242-246 `_make_conv_level`) through
  * conv_small, the engine's kernel for them: C -> N in {16 -> 16, 16 -> 32, 32 -> 32 (stride 1),

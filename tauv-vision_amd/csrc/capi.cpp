@@ -184,28 +184,82 @@ int tv_engine_create(const tv_model_desc* d, const tv_weight_view* w, int32_t n,
   })
 }
 
+// "NAME=VALUE;NAME=VALUE" -> pairs (tv_engine_create_diag, tv_diag_pack_op)
+static int parse_knobs(const char* knobs, std::vector<std::pair<std::string, std::string>>* kv) {
+  for (const char* c = knobs ? knobs : ""; *c;) {
+    const char* e = c;
+    while (*e && *e != ';') ++e;
+    std::string item(c, e);
+    c = *e ? e + 1 : e;
+    if (item.empty()) continue;
+    const size_t eq = item.find('=');
+    if (eq == std::string::npos) { set_error("engine knob without '=': " + item); return TV_EINVAL; }
+    kv->emplace_back(item.substr(0, eq), item.substr(eq + 1));
+  }
+  return TV_OK;
+}
+
 int tv_engine_create_diag(const tv_model_desc* d, const tv_weight_view* w, int32_t n, int32_t device,
                           const char* knobs, tv_engine** out) {
   TV_GUARD({
     if (!d || !out || (n && !w)) { set_error("null argument"); return TV_EINVAL; }
     std::vector<std::pair<std::string, std::string>> kv;
-    for (const char* c = knobs ? knobs : ""; *c;) {
-      const char* e = c;
-      while (*e && *e != ';') ++e;
-      std::string item(c, e);
-      c = *e ? e + 1 : e;
-      if (item.empty()) continue;
-      const size_t eq = item.find('=');
-      if (eq == std::string::npos) { set_error("engine knob without '=': " + item); return TV_EINVAL; }
-      kv.emplace_back(item.substr(0, eq), item.substr(eq + 1));
-    }
+    int rc = parse_knobs(knobs, &kv);
+    if (rc) return rc;
     tv_engine* e = new tv_engine();
-    int rc = e->e.create(*d, w, n, device, kv);
+    rc = e->e.create(*d, w, n, device, kv);
     if (rc) {
       delete e;
       return rc;
     }
     *out = e;
+    return TV_OK;
+  })
+}
+
+int tv_diag_pack_op(const tv_model_desc* d, const tv_weight_view* w, int32_t n, const char* knobs, int32_t op,
+                    int32_t info[5], char* label, int32_t label_cap, int32_t (*segs)[6], int32_t seg_cap,
+                    int64_t size[3], void* weight, void* bias, void* extra, const int64_t cap[3]) {
+  TV_GUARD({
+    if (!d || !info || !size || (n && !w) || seg_cap < 0 || (seg_cap && !segs) || ((weight || bias || extra) && !cap)) {
+      set_error("null argument");
+      return TV_EINVAL;
+    }
+    std::vector<std::pair<std::string, std::string>> kv;
+    int rc = parse_knobs(knobs, &kv);
+    if (rc) return rc;
+    Engine e;
+    HostWeights host_w;
+    if ((rc = weight_views(w, n, &host_w)) || (rc = e.configure(*d, kv, 256))) return rc;
+    info[0] = (int32_t)e.plan.ops.size();
+    if (op < 0 || op >= info[0]) { set_error("op index out of range"); return TV_EINVAL; }
+    const OpSpec& o = e.plan.ops[op];
+    HostPacked hp;
+    if ((rc = pack_op_host(e.plan, op, e.dtype, host_w, e.stem_op, e.ct3_mode, &hp))) return rc;
+    info[1] = o.kind; info[2] = hp.Npad; info[3] = hp.Kpad; info[4] = (int32_t)o.segs.size();
+    if (label && label_cap > 0) {
+      std::strncpy(label, o.label.c_str(), label_cap - 1);
+      label[label_cap - 1] = 0;
+    }
+    for (int i = 0; i < info[4] && i < seg_cap; ++i) {
+      const SegSpec& sg = o.segs[i];
+      const int32_t row[6] = {sg.kh, sg.row_expand ? sg.row_expand : sg.kw, e.plan.tensors[sg.src].C, sg.ci0, sg.cin,
+                              i < (int)hp.seg_ksteps.size() ? hp.seg_ksteps[i] : 0};
+      std::memcpy(segs[i], row, sizeof(row));
+    }
+    // extra: the convt3 fragments, or the fused-head fragments + their fp32 bias + head_row0 / head_nrows
+    std::vector<uint8_t> ex = hp.w_ct3;
+    if (!hp.head_w.empty()) {
+      ex = hp.head_w;
+      const uint8_t* b = reinterpret_cast<const uint8_t*>(hp.head_b.data());
+      ex.insert(ex.end(), b, b + hp.head_b.size() * sizeof(float));
+      for (const int* a : {hp.head_row0, hp.head_nrows})
+        ex.insert(ex.end(), reinterpret_cast<const uint8_t*>(a), reinterpret_cast<const uint8_t*>(a + 16));
+    }
+    size[0] = (int64_t)hp.w.size(); size[1] = (int64_t)(hp.bias.size() * sizeof(float)); size[2] = (int64_t)ex.size();
+    if (weight && size[0] && cap[0] == size[0]) std::memcpy(weight, hp.w.data(), size[0]);
+    if (bias && size[1] && cap[1] == size[1]) std::memcpy(bias, hp.bias.data(), size[1]);
+    if (extra && size[2] && cap[2] == size[2]) std::memcpy(extra, ex.data(), size[2]);
     return TV_OK;
   })
 }

@@ -7,28 +7,40 @@
 #include <vector>
 
 #include "common.h"
+#include "pack.h"
 #include "../../include/tauv_vision_amd.h"
 
 namespace {
-
-void put(std::vector<uint8_t>& buf, size_t i, float v, int dtype) {
-  if (dtype == tv::F32) {
-    std::memcpy(buf.data() + 4 * i, &v, 4);
-  } else if (dtype == tv::F16) {
-    const _Float16 h = (_Float16)v;
-    std::memcpy(buf.data() + 2 * i, &h, 2);
-  } else {
-    const uint16_t b = tv::f32_to_bf16(v);
-    std::memcpy(buf.data() + 2 * i, &b, 2);
-  }
-}
 
 struct DevBuf {
   void* p = nullptr;
   ~DevBuf() {
     if (p) (void)hipFree(p);
   }
+  int upload(const void* src, size_t bytes) {  // a fresh allocation holding a copy of host memory
+    TV_HIP(hipMalloc(&p, bytes));
+    TV_HIP(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
+    return TV_OK;
+  }
+  template <class T>
+  int upload(const std::vector<T>& v) { return upload(v.data(), v.size() * sizeof(T)); }
 };
+
+// compute units of the current device (256 when the query fails)
+int device_cus(int* ncu) {
+  int dev = 0;
+  *ncu = 256;
+  TV_HIP(hipGetDevice(&dev));
+  if (hipDeviceGetAttribute(ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || *ncu < 1) *ncu = 256;
+  return TV_OK;
+}
+
+// a host fp32 bias [N] zero-padded to Npad
+std::vector<float> padded_bias(const float* bias, int N, int Npad) {
+  std::vector<float> hb(Npad, 0.f);
+  std::memcpy(hb.data(), bias, N * sizeof(float));
+  return hb;
+}
 
 }  // namespace
 
@@ -38,7 +50,7 @@ namespace tv {
 // centerpoint_dla.py:389-391; 3x3, stride 1, pad 1) + bias + activation, as the engine runs it:
 // variant 0 = fused dcn_gemm (32-channel k-steps), 1 = fused dcn_gemm64 (tile by size),
 // 2 = dcn_gemm64 with 64-pixel tiles, 3 = unfused (dcn_sample column tensor + implicit GEMM: the
-// fp32 path), 4 = dcn_win (C == N == 64), 5 = dcn_gemm64d (gathers two k-steps ahead). weight: host fp32 [N][C][3][3] (PyTorch layout), K packed tap-major as the engine does.
+// fp32 path), 4 = dcn_win (C == N == 64), 5 = dcn_gemm64d (gathers two k-steps ahead). weight: host fp32 [N][C][3][3] (PyTorch layout), placed by the engine's packer (pack.h).
 int diag_dcn_conv(const void* x, const void* om, int B, int H, int W, int C, int om_ldc, const float* weight,
                   const float* bias, int N, int act, int dtype, int variant, void* out, hipStream_t s) {
   if (!x || !om || !weight || !bias || !out || B < 1 || H < 1 || W < 1 || C < 1 || N < 1 || om_ldc < 27 ||
@@ -56,18 +68,12 @@ int diag_dcn_conv(const void* x, const void* om, int B, int H, int W, int C, int
   const int ksteps = (K + BK - 1) / BK;
   const int Kpad = ksteps * BK;
   const int Npad = (N + 127) / 128 * 128;
-  std::vector<uint8_t> hw((size_t)Npad * Kpad * esz, 0);
-  for (int n = 0; n < N; ++n)
-    for (int c = 0; c < C; ++c)
-      for (int t = 0; t < 9; ++t) put(hw, (size_t)n * Kpad + (size_t)t * C + c, weight[((size_t)n * C + c) * 9 + t], dtype);
-  std::vector<float> hb(Npad, 0.f);
-  std::memcpy(hb.data(), bias, N * sizeof(float));
+  std::vector<float> hw((size_t)Npad * Kpad, 0.f);
+  place_weight(hw, Kpad, 0, 0, weight, N, C, 9, 0, C, C);
   DevBuf dw, db, dcols, dpar, dzero, dslab, dcnt;
-  TV_HIP(hipMalloc(&dw.p, hw.size()));
-  TV_HIP(hipMemcpy(dw.p, hw.data(), hw.size(), hipMemcpyHostToDevice));
-  TV_HIP(hipMalloc(&db.p, hb.size() * 4));
-  TV_HIP(hipMemcpy(db.p, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
-  int rc = 0;
+  int rc = dw.upload(to_dtype(hw, dtype));
+  if (!rc) rc = db.upload(padded_bias(bias, N, Npad));
+  if (rc) return rc;
   if (variant != 3) {
     DcnParams q{};
     q.x = x;
@@ -93,9 +99,8 @@ int diag_dcn_conv(const void* x, const void* om, int B, int H, int W, int C, int
       set_error("diag_dcn_conv: dcn_win needs C == N == 64");
       return TV_EINVAL;
     }
-    int dev = 0, cus = 0;
-    TV_HIP(hipGetDevice(&dev));
-    TV_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    int cus = 0;
+    if ((rc = device_cus(&cus))) return rc;
     int mode = variant == 4 ? 3 : variant;
     if (variant >= 6) {  // dcn_gemm64 on 64-pixel tiles, split-K over 3 / 4 / 9 tap ranges
       mode = 2;
@@ -131,8 +136,7 @@ int diag_dcn_conv(const void* x, const void* om, int B, int H, int W, int C, int
       p.mtiles = (p.M + 127) / 128;
       p.ntiles = Npad / 128;
       p.zero = dzero.p;
-      TV_HIP(hipMalloc(&dpar.p, sizeof(ConvParams)));
-      TV_HIP(hipMemcpy(dpar.p, &p, sizeof(ConvParams), hipMemcpyHostToDevice));
+      if ((rc = dpar.upload(&p, sizeof(ConvParams)))) return rc;
       rc = launch_conv(p, (const ConvParams*)dpar.p, out, dtype, 0, 0, s);
     }
   }
@@ -145,7 +149,7 @@ int diag_dcn_conv(const void* x, const void* om, int B, int H, int W, int C, int
 // streaming kernel the engine uses for stride-1 1x1 layers (conv1x1.hip): nseg inputs of M pixels,
 // segment k compute-dtype [M][ldc[k]] with C[k] channels; weight host fp32 [N][sum C] (the
 // concatenated input channels in segment order), bias host fp32 [N]; out compute-dtype [M][out_ldc].
-// Packed as the engine packs a Root: segment k's channels at k-step kbase[k] (128-byte k-steps).
+// Placed by the engine's packer as a Root: segment k's channels at k-step kbase[k] (128-byte k-steps).
 int diag_conv1x1(const void* const* src, const int* C, const int* ldc, int nseg, int M, const float* weight,
                  const float* bias, int N, int act, int dtype, void* out, int out_ldc, hipStream_t s) {
   if (!src || !C || !ldc || !weight || !bias || !out || nseg < 1 || nseg > kMaxSeg || M < 1 || N < 1 || act < 0 ||
@@ -169,17 +173,11 @@ int diag_conv1x1(const void* const* src, const int* C, const int* ldc, int nseg,
   }
   const int Kpad = kbase * BK;
   const int Npad = (N + 127) / 128 * 128;
-  std::vector<uint8_t> hw((size_t)Npad * Kpad * esz, 0);
-  for (int n = 0; n < N; ++n) {
-    int c0 = 0;
-    for (int k = 0; k < nseg; ++k) {
-      for (int c = 0; c < C[k]; ++c)
-        put(hw, (size_t)n * Kpad + (size_t)p.seg[k].kbase * BK + c, weight[(size_t)n * ctot + c0 + c], dtype);
-      c0 += C[k];
-    }
+  std::vector<float> hw((size_t)Npad * Kpad, 0.f);
+  for (int k = 0, c0 = 0; k < nseg; ++k) {  // the weight is K-ordered already: one tap, ci0 = the column offset
+    place_weight(hw, Kpad, 0, (size_t)p.seg[k].kbase * BK, weight, N, ctot, 1, c0, C[k], C[k]);
+    c0 += C[k];
   }
-  std::vector<float> hb(Npad, 0.f);
-  std::memcpy(hb.data(), bias, N * sizeof(float));
   p.nseg = nseg;
   p.Ho = 1;
   p.Wo = M;
@@ -194,24 +192,20 @@ int diag_conv1x1(const void* const* src, const int* C, const int* ldc, int nseg,
     return TV_EINVAL;
   }
   DevBuf dw, db, dpar;
-  TV_HIP(hipMalloc(&dw.p, hw.size()));
-  TV_HIP(hipMemcpy(dw.p, hw.data(), hw.size(), hipMemcpyHostToDevice));
-  TV_HIP(hipMalloc(&db.p, hb.size() * 4));
-  TV_HIP(hipMemcpy(db.p, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
+  int rc = dw.upload(to_dtype(hw, dtype)), ncu = 0;
+  if (!rc) rc = db.upload(padded_bias(bias, N, Npad));
   p.weight = dw.p;
   p.bias = (const float*)db.p;
-  TV_HIP(hipMalloc(&dpar.p, sizeof(ConvParams)));
-  TV_HIP(hipMemcpy(dpar.p, &p, sizeof(ConvParams), hipMemcpyHostToDevice));
-  int dev = 0, ncu = 256;
-  TV_HIP(hipGetDevice(&dev));
-  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) ncu = 256;
-  const int rc = launch_conv1x1_stream(p, (const ConvParams*)dpar.p, dtype, ncu, s);
+  if (!rc) rc = dpar.upload(&p, sizeof(ConvParams));
+  if (!rc) rc = device_cus(&ncu);
+  if (rc) return rc;
+  rc = launch_conv1x1_stream(p, (const ConvParams*)dpar.p, dtype, ncu, s);
   if (rc) return rc == TV_EHIP ? rc : TV_EINVAL;
   TV_HIP(hipStreamSynchronize(s));  // the staging buffers are freed on return
   return TV_OK;
 }
 
-// One conv through the one-shot small-level kernel (conv_burst.hip), packed as the engine packs a
+// One conv through the one-shot small-level kernel (conv_burst.hip), placed by the engine's packer as a
 // multi-segment conv: segment k = a kxk (k = 1 or 3, pad k / 2) conv at `stride` over
 // src[k] (compute dtype NHWC [B, H, W, ldc], C channels); geom[6 k ..] = H, W, C, ldc, k, stride;
 // weight host fp32 [N][K], K = segment-major, tap-major, channel-minor; bias host fp32 [N];
@@ -243,15 +237,11 @@ int diag_conv_burst(const void* const* src, const int* geom, int nseg, int B, in
   }
   const int Kpad = kbase * BK;
   const int Npad = (N + 127) / 128 * 128;
-  std::vector<uint8_t> hw((size_t)Npad * Kpad * 2, 0);
-  for (int n = 0; n < N; ++n)
-    for (int k = 0; k < nseg; ++k) {
-      const int kk = geom[6 * k + 4], C = geom[6 * k + 2];
-      for (int t = 0; t < kk * kk * C; ++t)
-        put(hw, (size_t)n * Kpad + (size_t)p.seg[k].kbase * BK + t, weight[(size_t)n * ktot + koff[k] + t], dtype);
-    }
-  std::vector<float> hb(Npad, 0.f);
-  std::memcpy(hb.data(), bias, N * sizeof(float));
+  std::vector<float> hw((size_t)Npad * Kpad, 0.f);
+  for (int k = 0; k < nseg; ++k) {  // the weight is K-ordered already: one tap, ci0 = the segment's column offset
+    const int K = p.seg[k].kh * p.seg[k].kw * p.seg[k].C;
+    place_weight(hw, Kpad, 0, (size_t)p.seg[k].kbase * BK, weight, N, ktot, 1, koff[k], K, K);
+  }
   p.nseg = nseg;
   p.Ho = Ho;
   p.Wo = Wo;
@@ -262,10 +252,9 @@ int diag_conv_burst(const void* const* src, const int* geom, int nseg, int B, in
   p.out = out;
   p.out_ldc = out_ldc;
   DevBuf dw, db, dwb;
-  TV_HIP(hipMalloc(&dw.p, hw.size()));
-  TV_HIP(hipMemcpy(dw.p, hw.data(), hw.size(), hipMemcpyHostToDevice));
-  TV_HIP(hipMalloc(&db.p, hb.size() * 4));
-  TV_HIP(hipMemcpy(db.p, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
+  int rc = dw.upload(to_dtype(hw, dtype));
+  if (!rc) rc = db.upload(padded_bias(bias, N, Npad));
+  if (rc) return rc;
   p.weight = dw.p;
   p.bias = (const float*)db.p;
   BurstParams bp{};
@@ -274,7 +263,7 @@ int diag_conv_burst(const void* const* src, const int* geom, int nseg, int B, in
     return TV_EINVAL;
   }
   TV_HIP(hipMalloc(&dwb.p, conv_burst_weight_bytes(bp)));
-  int rc = conv_burst_repack(dw.p, Kpad, 2, bp, dwb.p, s);
+  rc = conv_burst_repack(dw.p, Kpad, 2, bp, dwb.p, s);
   if (!rc) {
     bp.w = dwb.p;
     const BurstParams* pp = &bp;
@@ -349,10 +338,10 @@ int diag_convt3(const void* src, int B, int H, int W, int C, int ldc, const floa
   std::vector<uint8_t> hw(convt3_weight_bytes(C, N));
   convt3_pack(weight, C, N, dtype, hw.data());
   DevBuf dw, db;
-  TV_HIP(hipMalloc(&dw.p, hw.size()));
-  TV_HIP(hipMemcpy(dw.p, hw.data(), hw.size(), hipMemcpyHostToDevice));
-  TV_HIP(hipMalloc(&db.p, (size_t)N * 4));
-  TV_HIP(hipMemcpy(db.p, bias, (size_t)N * 4, hipMemcpyHostToDevice));
+  int rc = dw.upload(hw), ncu = 0;
+  if (!rc) rc = db.upload(bias, (size_t)N * 4);
+  if (!rc) rc = device_cus(&ncu);
+  if (rc) return rc;
   ConvT3Params p{};
   p.src = src;
   p.B = B;
@@ -368,10 +357,7 @@ int diag_convt3(const void* src, int B, int H, int W, int C, int ldc, const floa
   p.N = N;
   p.tw = tw;
   p.tr = tr;
-  int dev = 0, ncu = 256;
-  TV_HIP(hipGetDevice(&dev));
-  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) ncu = 256;
-  const int rc = launch_convt3(p, dtype, ncu, s);
+  rc = launch_convt3(p, dtype, ncu, s);
   if (rc) return rc == TV_EHIP ? rc : TV_EINVAL;
   TV_HIP(hipStreamSynchronize(s));  // the staging buffers are freed on return
   return TV_OK;
@@ -379,7 +365,7 @@ int diag_convt3(const void* src, int B, int H, int W, int C, int ldc, const floa
 
 // One narrow-channel 3x3 pad-1 conv + bias + activation through conv_small.hip (the engine's kernel
 // for DLA-34's full-resolution base levels, centerpoint_dla.py:242-246): weight host fp32
-// [N][C][3][3] packed as the engine packs it ([N][Kpad], K tap-major, channel-minor); halo selects
+// [N][C][3][3] placed by the engine's packer ([N][Kpad], K tap-major, channel-minor; no row padding); halo selects
 // the LDS-halo variant.
 int diag_conv_small(const void* src, int B, int H, int W, int C, int ldc, const float* weight, const float* bias,
                     int N, int stride, int act, int dtype, int halo, void* out, int out_ldc, hipStream_t s) {
@@ -389,10 +375,8 @@ int diag_conv_small(const void* src, int B, int H, int W, int C, int ldc, const 
     return TV_EINVAL;
   }
   const int Kpad = (9 * C + 63) / 64 * 64;
-  std::vector<uint8_t> hw((size_t)N * Kpad * 2, 0);
-  for (int n = 0; n < N; ++n)
-    for (int c = 0; c < C; ++c)
-      for (int t = 0; t < 9; ++t) put(hw, (size_t)n * Kpad + t * C + c, weight[((size_t)n * C + c) * 9 + t], dtype);
+  std::vector<float> hw((size_t)N * Kpad, 0.f);
+  place_weight(hw, Kpad, 0, 0, weight, N, C, 9, 0, C, C);
   ConvParams p{};
   p.seg[0] = ConvSegment{src, H, W, C, ldc, 3, 3, stride, 1, 1, Kpad / 64, 0};
   p.nseg = 1;
@@ -405,18 +389,14 @@ int diag_conv_small(const void* src, int B, int H, int W, int C, int ldc, const 
   p.out = out;
   p.out_ldc = out_ldc;
   DevBuf dw, db, dp;
-  TV_HIP(hipMalloc(&dw.p, hw.size()));
-  TV_HIP(hipMemcpy(dw.p, hw.data(), hw.size(), hipMemcpyHostToDevice));
-  TV_HIP(hipMalloc(&db.p, (size_t)N * 4));
-  TV_HIP(hipMemcpy(db.p, bias, (size_t)N * 4, hipMemcpyHostToDevice));
+  int rc = dw.upload(to_dtype(hw, dtype)), ncu = 0;
+  if (!rc) rc = db.upload(bias, (size_t)N * 4);
   p.weight = dw.p;
   p.bias = (const float*)db.p;
-  TV_HIP(hipMalloc(&dp.p, sizeof(ConvParams)));
-  TV_HIP(hipMemcpy(dp.p, &p, sizeof(ConvParams), hipMemcpyHostToDevice));
-  int dev = 0, ncu = 256;
-  TV_HIP(hipGetDevice(&dev));
-  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) ncu = 256;
-  const int rc = launch_conv_small(p, (const ConvParams*)dp.p, dtype, ncu, halo, s);
+  if (!rc) rc = dp.upload(&p, sizeof(ConvParams));
+  if (!rc) rc = device_cus(&ncu);
+  if (rc) return rc;
+  rc = launch_conv_small(p, (const ConvParams*)dp.p, dtype, ncu, halo, s);
   if (rc) return rc == TV_EHIP ? rc : TV_EINVAL;
   TV_HIP(hipStreamSynchronize(s));
   return TV_OK;

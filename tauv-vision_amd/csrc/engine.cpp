@@ -1,291 +1,46 @@
-// Engine: BN folding + weight packing at create, liveness-planned HBM workspace per
-// (stream, batch), and the launch sequence of one forward. C ABI in capi.cpp.
+// Engine: create (configure on the host, then upload the host-packed weights of pack.cpp),
+// liveness-planned HBM workspace per (stream, batch), and the launch sequence of one forward.
+// C ABI in capi.cpp.
 #include "engine.h"
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <cstdlib>
 #include <memory>
-#include <set>
 
 namespace tv {
 
-namespace {
-
-void store_elem(void* base, size_t i, float v, int dtype) {
-  if (dtype == F32) {
-    reinterpret_cast<float*>(base)[i] = v;
-  } else if (dtype == F16) {
-    reinterpret_cast<_Float16*>(base)[i] = (_Float16)v;
-  } else {
-    reinterpret_cast<uint16_t*>(base)[i] = f32_to_bf16(v);
-  }
-}
-
-}  // namespace
-
-const float* Engine::weight(const std::string& name, int64_t numel) {
-  auto it = host_w.find(name);
-  if (it == host_w.end()) {
-    set_error("missing state_dict key: " + name);
-    return nullptr;
-  }
-  if (it->second.second != numel) {
-    set_error("state_dict key " + name + ": expected " + std::to_string(numel) + " elements, got " +
-              std::to_string(it->second.second));
-    return nullptr;
-  }
-  return it->second.first;
-}
-
-// Folded BN affine for a conv `p` (+ BatchNorm `bn`): scale, shift per output channel.
-int Engine::fold(const std::string& conv, const std::string& bn, int cout, std::vector<double>& scale,
-                 std::vector<double>& shift) {
-  scale.assign(cout, 1.0);
-  shift.assign(cout, 0.0);
-  // bias=False convs (DLA34, centerpoint_dla.py:24-27) have no `.bias` key in the layout
-  std::vector<float> zeros;
-  const float* b = nullptr;
-  if (plan.names.count(conv + ".bias")) {
-    b = weight(conv + ".bias", cout);
-    if (!b) return TV_ENOTFOUND;
-  } else {
-    zeros.assign(cout, 0.f);
-    b = zeros.data();
-  }
-  for (int i = 0; i < cout; ++i) shift[i] = b[i];
-  if (bn.empty()) return TV_OK;
-  const float* g = weight(bn + ".weight", cout);
-  const float* be = weight(bn + ".bias", cout);
-  const float* mu = weight(bn + ".running_mean", cout);
-  const float* var = weight(bn + ".running_var", cout);
-  if (!g || !be || !mu || !var) return TV_ENOTFOUND;
-  for (int i = 0; i < cout; ++i) {
-    double s = (double)g[i] / std::sqrt((double)var[i] + 1e-5);
-    scale[i] = s;
-    shift[i] = ((double)b[i] - (double)mu[i]) * s + (double)be[i];
-  }
-  return TV_OK;
-}
-
+// Op i's weights: packed on the host (pack.cpp), uploaded, and the host copy released.
 int Engine::pack_op(size_t oi) {
-  const OpSpec& op = plan.ops[oi];
+  HostPacked hp;
+  int rc = pack_op_host(plan, oi, dtype, host_w, stem_op, ct3_mode, &hp);
+  if (rc) return rc;
   Packed& pk = packed[oi];
-  const int esz = dtype_size(dtype);
-  const int BK = 128 / esz;
-  if (op.kind == OP_PREP || op.kind == OP_MAXPOOL || op.kind == OP_DCN || op.kind == OP_LAYOUT_IN ||
-      op.kind == OP_BILINEAR_ADD || op.kind == OP_HEAD_SCATTER || op.kind == OP_MAXPOOL3S2 || op.kind == OP_ADD_RELU ||
-      op.kind == OP_STORE_F32)
-    return TV_OK;
-  if (op.kind == OP_DWCONVT_ADD) {  // depthwise ConvTranspose2d weight [C][1][2f][2f] -> fp32 [2f][2f][C]
-    const int c = op.N, k = 2 * op.up_s;
-    const float* w = weight(op.up_w + ".weight", (int64_t)c * k * k);
-    if (!w) return TV_ENOTFOUND;
-    std::vector<float> t((size_t)k * k * c);
-    for (int co = 0; co < c; ++co)
-      for (int tap = 0; tap < k * k; ++tap) t[(size_t)tap * c + co] = w[(size_t)co * k * k + tap];
-    TV_HIP(hipMalloc(&pk.w, t.size() * sizeof(float)));
-    TV_HIP(hipMemcpy(pk.w, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
-    weight_bytes += t.size() * sizeof(float);
-    return TV_OK;
-  }
-
-  std::vector<float> hw;    // [Npad][Kpad] fp32 staging
-  std::vector<float> bias;  // [Npad]
-  if (op.kind == OP_CONVT_ADD) {
-    const TensorSpec& src = plan.tensors[op.src];
-    const int c = op.N, s = op.up_s, cin = src.C;
-    const int N = s * s * c;
-    pk.Npad = (int)align_up(N, kTile);
-    pk.seg_ksteps = {(cin + BK - 1) / BK};
-    pk.Kpad = pk.seg_ksteps[0] * BK;
-    hw.assign((size_t)pk.Npad * pk.Kpad, 0.f);
-    bias.assign(pk.Npad, 0.f);
-    const float* w = weight(op.up_w + ".weight", (int64_t)cin * c * s * s);
-    const float* b = weight(op.up_w + ".bias", c);
-    if (!w || !b) return TV_ENOTFOUND;
-    for (int i = 0; i < s; ++i)
-      for (int j = 0; j < s; ++j)
-        for (int co = 0; co < c; ++co) {
-          const int n = (i * s + j) * c + co;
-          bias[n] = b[co];
-          for (int ci = 0; ci < cin; ++ci) hw[(size_t)n * pk.Kpad + ci] = w[(((size_t)ci * c + co) * s + i) * s + j];
-        }
-  } else {
-    const int N = op.N;
-    // rows of the PyTorch weight: a plain conv into the caller's fp32 output stores out_cpad
-    // columns of an out_c-channel conv (protonet _output_layer)
-    const int wN = (op.out < 0 && op.stack_w.empty()) ? plan.outspec(op.out).C : N;
-    pk.Npad = (int)align_up(N, kTile);
-    int kbase = 0;
-    pk.seg_ksteps.clear();
-    for (const SegSpec& sg : op.segs) {
-      const int cs = plan.tensors[sg.src].C;
-      const int ks = (sg.kh * sg.kw * cs + BK - 1) / BK;
-      pk.seg_ksteps.push_back(ks);
-      kbase += ks;
-    }
-    pk.Kpad = kbase * BK;
-    hw.assign((size_t)pk.Npad * pk.Kpad, 0.f);
-    bias.assign(pk.Npad, 0.f);
-    if (!op.stack_w.empty()) {
-      // stacked heads (3x3, single segment) or block-diagonal 1x1 heads
-      const SegSpec& sg = op.segs[0];
-      const int cs = plan.tensors[sg.src].C;
-      const bool diag = !op.diag_in_off.empty();
-      int row = 0;
-      for (size_t h = 0; h < op.stack_w.size(); ++h) {
-        const int n = op.stack_n[h];
-        const int cin = diag ? plan.tensors[sg.src].C / (int)op.stack_w.size() : sg.cin;
-        const int k = sg.kh;
-        const float* w = weight(op.stack_w[h] + ".weight", (int64_t)n * cin * k * k);
-        const float* b = weight(op.stack_w[h] + ".bias", n);
-        if (!w || !b) return TV_ENOTFOUND;
-        const int r0 = diag ? op.diag_out_off[h] : row;
-        const int c0 = diag ? op.diag_in_off[h] : 0;
-        for (int co = 0; co < n; ++co) {
-          bias[r0 + co] = b[co];
-          for (int ci = 0; ci < cin; ++ci)
-            for (int t = 0; t < k * k; ++t)
-              hw[(size_t)(r0 + co) * pk.Kpad + t * cs + c0 + ci] = w[((size_t)co * cin + ci) * k * k + t];
-        }
-        row += n;
-      }
-    } else {
-      // BN-folded segments; bias = sum over the distinct convs feeding this GEMM
-      std::set<std::string> seen;
-      int kb = 0;
-      for (size_t si = 0; si < op.segs.size(); ++si) {
-        const SegSpec& sg = op.segs[si];
-        const int cs = plan.tensors[sg.src].C;
-        if (sg.identity) {  // residual added as-is: identity 1x1 (exact in every compute dtype)
-          // ... or through an eval BatchNorm that follows a ReLU and so folds into no conv (YOLACT
-          // head blocks): the identity scaled per channel, the shift in the bias
-          std::vector<double> scale(N, 1.0), shift(N, 0.0);
-          if (!sg.bn.empty()) {
-            int rc = fold("", sg.bn, N, scale, shift);
-            if (rc) return rc;
-          }
-          for (int co = 0; co < std::min(N, sg.cin); ++co) {
-            hw[(size_t)co * pk.Kpad + (size_t)kb * BK + co] = (float)scale[co];
-            bias[co] += (float)shift[co];
-          }
-          kb += pk.seg_ksteps[si];
-          continue;
-        }
-        // total input channels of the PyTorch weight = max over segments sharing it
-        int wcin = 0;
-        for (const SegSpec& o : op.segs)
-          if (o.wname == sg.wname) wcin = std::max(wcin, o.ci0 + o.cin);
-        const int re = sg.row_expand;  // row-expanded input: K index = ky * cs + kx * cin + c
-        const int kk = re ? sg.kh * re : sg.kh * sg.kw;
-        if (sg.convt_phase >= 0) {
-          // ConvTranspose2d(3, s2, p1) weight [cin][cout][3][3], one output parity (pi, pj): tap
-          // (dy, dx) of the phase conv reads input (m + dy, n + dx) and uses kernel element
-          // ky = 1 (pi = 0) or 2 - 2 dy (pi = 1) — out[2m + pi] += x[m + dy] W[ky] with
-          // 2m + pi = 2(m + dy) - 1 + ky — and kx likewise
-          const float* w = weight(sg.wname + ".weight", (int64_t)wcin * wN * 9);
-          if (!w) return TV_ENOTFOUND;
-          std::vector<double> scale, shift;
-          int rc = fold(sg.wname, "", wN, scale, shift);
-          if (rc) return rc;
-          for (int co = 0; co < wN; ++co) bias[co] += (float)shift[co];
-          const int pi = sg.convt_phase >> 1, pj = sg.convt_phase & 1;
-          for (int dy = 0; dy < sg.kh; ++dy)
-            for (int dx = 0; dx < sg.kw; ++dx) {
-              const int ky = pi == 0 ? 1 : 2 - 2 * dy, kx = pj == 0 ? 1 : 2 - 2 * dx;
-              const int t = dy * sg.kw + dx;
-              for (int co = 0; co < wN; ++co)
-                for (int ci = 0; ci < sg.cin; ++ci)
-                  hw[(size_t)co * pk.Kpad + (size_t)kb * BK + (size_t)t * cs + ci] =
-                      w[(((size_t)(sg.ci0 + ci) * wN + co) * 3 + ky) * 3 + kx];
-            }
-          // all four phases in one launch (convt3.hip): the phase-(0,0) op carries the whole
-          // ConvTranspose2d's weight in that kernel's fragment order (knob TV_CT3=0: off)
-          if (ct3_mode && dtype != F32 && sg.convt_phase == 0 && op.segs.size() == 1 && sg.ci0 == 0 &&
-              sg.cin == cs && wcin == cs && convt3_supported(cs, wN, cs, wN, 1, 1, esz)) {
-            std::vector<uint8_t> frag(convt3_weight_bytes(cs, wN));
-            convt3_pack(w, cs, wN, dtype, frag.data());
-            TV_HIP(hipMalloc(&pk.w_ct3, frag.size()));
-            TV_HIP(hipMemcpy(pk.w_ct3, frag.data(), frag.size(), hipMemcpyHostToDevice));
-            weight_bytes += frag.size();
-          }
-          kb += pk.seg_ksteps[si];
-          continue;
-        }
-        const float* w = weight(sg.wname + ".weight", (int64_t)wN * wcin * kk);
-        if (!w) return TV_ENOTFOUND;
-        std::vector<double> scale, shift;
-        int rc = fold(sg.wname, sg.bn, wN, scale, shift);
-        if (rc) return rc;
-        if (seen.insert(sg.wname).second)
-          for (int co = 0; co < wN; ++co) bias[co] += (float)shift[co];
-        for (int co = 0; co < wN; ++co)
-          for (int ci = 0; ci < sg.cin; ++ci)
-            for (int t = 0; t < kk; ++t) {
-              const size_t k = re ? (size_t)(t / re) * cs + (t % re) * sg.cin + ci : (size_t)t * cs + ci;
-              hw[(size_t)co * pk.Kpad + (size_t)kb * BK + k] =
-                  (float)((double)w[((size_t)co * wcin + sg.ci0 + ci) * kk + t] * scale[co]);
-            }
-        kb += pk.seg_ksteps[si];
-      }
-    }
-  }
-  // fused 1x1 heads (conv3x3 EPI 1): per 128-channel tile nt of the hidden (stacked 3x3) output,
-  // fragment (k-step j, lane l) = 8 weights W2[row0 + l%32][128nt + 16j + 8(l/32) + e]
-  if (dtype != F32 && !op.diag_in_off.empty() && op.segs.size() == 1) {
-    const int K = plan.tensors[op.segs[0].src].C;  // hidden channels
-    const int nts = K / 128;
-    const int hid = K / (int)op.stack_w.size();    // hidden channels per head
-    bool ok = K % 128 == 0 && nts <= 16 && hid % 128 == 0;
-    for (size_t h = 0; h < op.stack_n.size(); ++h) ok = ok && op.stack_n[h] <= 32;
-    if (ok) {
-      std::vector<uint8_t> frag((size_t)nts * 8 * 64 * 16, 0);
-      std::vector<float> hb((size_t)nts * 32, 0.f);
-      for (int nt = 0; nt < nts; ++nt) {
-        const int h = nt * 128 / hid;
-        const int row0 = op.diag_out_off[h], nr = op.stack_n[h];
-        pk.head_row0[nt] = row0;
-        pk.head_nrows[nt] = nr;
-        if (nt * 128 == op.diag_in_off[h])
-          for (int r = 0; r < nr; ++r) hb[nt * 32 + r] = bias[row0 + r];
-        for (int j = 0; j < 8; ++j)
-          for (int l = 0; l < 64; ++l)
-            for (int e = 0; e < 8; ++e) {
-              const int r = l & 31, k = nt * 128 + 16 * j + 8 * (l >> 5) + e;
-              const float v = r < nr ? hw[(size_t)(row0 + r) * pk.Kpad + k] : 0.f;
-              store_elem(frag.data(), ((size_t)(nt * 8 + j) * 64 + l) * 8 + e, v, dtype);
-            }
-      }
-      TV_HIP(hipMalloc(&pk.head_w, frag.size()));
-      TV_HIP(hipMemcpy(pk.head_w, frag.data(), frag.size(), hipMemcpyHostToDevice));
-      TV_HIP(hipMalloc((void**)&pk.head_b, hb.size() * sizeof(float)));
-      TV_HIP(hipMemcpy(pk.head_b, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice));
-      pk.head_ok = 1;
-    }
-  }
-  // device copies
-  std::vector<uint8_t> hbuf((size_t)pk.Npad * pk.Kpad * esz);
-  for (size_t i = 0; i < hw.size(); ++i) store_elem(hbuf.data(), i, hw[i], dtype);
-  if ((int)oi == stem_op) {  // stem.hip streams its weights in MFMA B-fragment order
-    std::vector<uint8_t> frag(stem_weight_bytes());
-    stem_fragment_order(reinterpret_cast<const uint16_t*>(hbuf.data()), pk.Npad, pk.Kpad,
-                        reinterpret_cast<uint16_t*>(frag.data()));
-    hbuf.swap(frag);
-  }
-  TV_HIP(hipMalloc(&pk.w, hbuf.size()));
-  TV_HIP(hipMemcpy(pk.w, hbuf.data(), hbuf.size(), hipMemcpyHostToDevice));
-  TV_HIP(hipMalloc((void**)&pk.bias, bias.size() * sizeof(float)));
-  TV_HIP(hipMemcpy(pk.bias, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
-  weight_bytes += hbuf.size() + bias.size() * 4;
+  pk.Npad = hp.Npad;
+  pk.Kpad = hp.Kpad;
+  pk.seg_ksteps = hp.seg_ksteps;
+  std::copy(hp.head_row0, hp.head_row0 + 16, pk.head_row0);
+  std::copy(hp.head_nrows, hp.head_nrows + 16, pk.head_nrows);
+  pk.head_ok = !hp.head_w.empty();
+  auto upload = [](auto*& dst, const auto& src) {
+    if (src.empty()) return (int)TV_OK;
+    const size_t bytes = src.size() * sizeof(src[0]);
+    TV_HIP(hipMalloc((void**)&dst, bytes));
+    TV_HIP(hipMemcpy(dst, src.data(), bytes, hipMemcpyHostToDevice));
+    return (int)TV_OK;
+  };
+  if ((rc = upload(pk.w_ct3, hp.w_ct3)) || (rc = upload(pk.head_w, hp.head_w)) || (rc = upload(pk.head_b, hp.head_b)) ||
+      (rc = upload(pk.w, hp.w)) || (rc = upload(pk.bias, hp.bias)))
+    return rc;
+  weight_bytes += hp.w_ct3.size() + hp.w.size() + hp.bias.size() * 4;
   return TV_OK;
 }
 
-int Engine::create(const tv_model_desc& d, const tv_weight_view* w, int n, int dev,
-                   const std::vector<std::pair<std::string, std::string>>& knobs) {
+// Every decision of create, on the host (no HIP call): the plan, the diagnostic knobs, and the
+// fusions that decide how an op's weights are packed. `cus` = the device's compute units.
+int Engine::configure(const tv_model_desc& d, const std::vector<std::pair<std::string, std::string>>& knobs, int cus) {
   desc = d;
-  device = dev;
+  cu_count = cus;
   if (desc.compute_dtype == TV_F32X3) {  // fp32 storage; the pipelined GEMMs' products as three fp16 MFMAs
     desc.compute_dtype = TV_F32;
     f32x3 = 1;
@@ -293,21 +48,6 @@ int Engine::create(const tv_model_desc& d, const tv_weight_view* w, int n, int d
   dtype = desc.compute_dtype;
   int rc = build_plan(desc, &plan);
   if (rc) return rc;
-  for (int i = 0; i < n; ++i) {
-    if (!w[i].name || (!w[i].data && w[i].numel)) {
-      set_error("null weight view");
-      return TV_EINVAL;
-    }
-    host_w[w[i].name] = {w[i].data, w[i].numel};
-  }
-  TV_HIP(hipSetDevice(device));
-  TV_HIP(hipMalloc(&zero_page, 256));
-  TV_HIP(hipMemset(zero_page, 0, 256));
-  {
-    int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0)
-      cu_count = ncu;
-  }
   // diagnostics only (tv_engine_create_diag): kernel-choice overrides for A/B experiments; the
   // product entry point (tv_engine_create) passes none and reads no environment
   for (const auto& kv : knobs) {
@@ -349,23 +89,11 @@ int Engine::create(const tv_model_desc& d, const tv_weight_view* w, int n, int d
     else if (k == "TV_CSM_HALO") csm_halo = std::max(0, std::min(2, v));
     else if (k == "TV_SLICES") slices = std::max(1, std::min(kMaxSlices, v));
     else if (k == "TV_SLICE_LAG") slice_lag = std::max(0, v);
-    else if (k == "TV_C3_STAMPS") {  // "op:device pointer" (stamp builds of conv3x3 only)
+    else if (k == "TV_C3_STAMPS") {  // "op:device pointer" (stamp builds of conv3x3 only; create checks the pointer)
 #if defined(TV_C3_EXP) && TV_C3_EXP == 9
       stamp_op = v;
       const char* c = std::strchr(env, ':');
       stamp_buf = c ? reinterpret_cast<unsigned long long*>(std::strtoull(c + 1, nullptr, 0)) : nullptr;
-      // the stamp kernel writes 8 counters per wave of every workgroup it may launch (<= one per
-      // CU, 8 waves): the pointer must lie in a device allocation with that much room after it
-      hipDeviceptr_t base = nullptr;
-      size_t size = 0;
-      const size_t need = (size_t)cu_count * 8 * 8 * sizeof(unsigned long long);
-      if (!stamp_buf || hipMemGetAddressRange(&base, &size, stamp_buf) != hipSuccess ||
-          (char*)stamp_buf + need > (char*)base + size) {
-        (void)hipGetLastError();
-        set_error("TV_C3_STAMPS: the pointer is not inside a device allocation of >= " + std::to_string(need) +
-                  " bytes");
-        return TV_EINVAL;
-      }
 #else
       set_error("TV_C3_STAMPS needs the stamp build of the library (EXTRA=-DTV_C3_EXP=9)");
       return TV_EINVAL;
@@ -445,6 +173,50 @@ int Engine::create(const tv_model_desc& d, const tv_weight_view* w, int n, int d
       if (ok) rstem_op = (int)i + 1;
       break;
     }
+  return TV_OK;
+}
+
+// The caller's weight views by name (valid during create only)
+int weight_views(const tv_weight_view* w, int n, HostWeights* host_w) {
+  for (int i = 0; i < n; ++i) {
+    if (!w[i].name || (!w[i].data && w[i].numel)) {
+      set_error("null weight view");
+      return TV_EINVAL;
+    }
+    (*host_w)[w[i].name] = {w[i].data, w[i].numel};
+  }
+  return TV_OK;
+}
+
+int Engine::create(const tv_model_desc& d, const tv_weight_view* w, int n, int dev,
+                   const std::vector<std::pair<std::string, std::string>>& knobs) {
+  device = dev;
+  int rc = weight_views(w, n, &host_w);
+  if (rc) return rc;
+  TV_HIP(hipSetDevice(device));
+  int ncu = 0;
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = cu_count;
+  rc = configure(d, knobs, ncu);
+  if (rc) return rc;
+#if defined(TV_C3_EXP) && TV_C3_EXP == 9
+  for (const auto& kv : knobs) {
+    if (kv.first != "TV_C3_STAMPS") continue;
+    // the stamp kernel writes 8 counters per wave of every workgroup it may launch (<= one per
+    // CU, 8 waves): the pointer must lie in a device allocation with that much room after it
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    const size_t need = (size_t)cu_count * 8 * 8 * sizeof(unsigned long long);
+    if (!stamp_buf || hipMemGetAddressRange(&base, &size, stamp_buf) != hipSuccess ||
+        (char*)stamp_buf + need > (char*)base + size) {
+      (void)hipGetLastError();
+      set_error("TV_C3_STAMPS: the pointer is not inside a device allocation of >= " + std::to_string(need) +
+                " bytes");
+      return TV_EINVAL;
+    }
+  }
+#endif
+  TV_HIP(hipMalloc(&zero_page, 256));
+  TV_HIP(hipMemset(zero_page, 0, 256));
   packed.resize(plan.ops.size());
   for (size_t i = 0; i < plan.ops.size(); ++i) {
     rc = pack_op(i);

@@ -2,12 +2,12 @@
 #include <map>
 #include <mutex>
 #include <string>
-#include <unordered_map>
 #include <utility>
 #include <variant>
 #include <vector>
 
 #include "common.h"
+#include "pack.h"
 #include "planner.h"
 
 namespace tv {
@@ -31,9 +31,6 @@ struct Packed {
   float* head_b = nullptr;
   int head_row0[16] = {}, head_nrows[16] = {};
 };
-
-constexpr int kTile = 128;
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // The one thing that happens when an op's turn comes. Chosen by plan_schedule (schedule.cpp);
 // run_op, op_kernel, run_all's grouped launches and profile() switch on it.
@@ -161,7 +158,7 @@ struct Engine {
   int ss2_op = -1;             // op index of block0.conv1 when it runs fused with the stem, else -1
   int rstem_mode = 1;          // ResNet stem + max-pool in one launch (stem7s2_pool) for fp16/bf16 (knob TV_RSTEM=0: the
                                // generic row-expanded stem + maxpool3x3s2, which the fp32 paths always take)
-  int rstem_op = -1;           // op index of the stride-2 7x7 stem conv when the plan has that shape (create), else -1
+  int rstem_op = -1;           // op index of the stride-2 7x7 stem conv when the plan has that shape (configure), else -1
   // concurrent slices: a batch of >= slices * slice_min frames runs as `slices` near-equal parts,
   // the first on the caller's stream and the others on side streams (fork / join events), so one
   // slice's latency-bound small layers and grid tails overlap another's large layers
@@ -181,9 +178,13 @@ struct Engine {
   std::map<void*, SideStreams> side;  // per caller stream
   std::mutex mu;
   std::map<std::pair<void*, int>, Workspace*> workspaces;
-  std::unordered_map<std::string, std::pair<const float*, int64_t>> host_w;  // during create only
+  HostWeights host_w;  // during create only
 
   ~Engine();
+  // create in two steps, like a workspace: configure() takes every decision on the host (the plan,
+  // the knobs, the fusions that change how an op is packed; no HIP call), then create() makes the
+  // zero page and uploads each op's host-packed weights (pack.h)
+  int configure(const tv_model_desc& d, const std::vector<std::pair<std::string, std::string>>& knobs, int cus);
   int create(const tv_model_desc& d, const tv_weight_view* w, int n, int dev,
              const std::vector<std::pair<std::string, std::string>>& knobs = {});
   int get_workspace(int B, hipStream_t s, Workspace** out);
@@ -218,10 +219,7 @@ struct Engine {
 
  private:
   void op_stored(const Workspace* ws, size_t i, int32_t shape[4]) const;
-  const float* weight(const std::string& name, int64_t numel);
-  int fold(const std::string& conv, const std::string& bn, int cout, std::vector<double>& scale,
-           std::vector<double>& shift);
-  int pack_op(size_t i);
+  int pack_op(size_t i);  // pack_op_host, upload, release the host copy
   void plan_schedule(int B, Workspace* ws) const;  // schedule.cpp: every decision, no HIP call
   int materialize(Workspace* ws);                  // the allocations, repacks, pointers and uploads of a planned workspace
   int bind_op(size_t i, Workspace* ws);
@@ -232,5 +230,8 @@ struct Engine {
   int run_all(const IoPtrs& io, int input_u8, int B, hipStream_t s, size_t op0 = 0, size_t op1 = (size_t)-1);
   int get_side(hipStream_t s, int n, SideStreams** out);
 };
+
+// The caller's weight views by name; TV_EINVAL for a null name or null data
+int weight_views(const tv_weight_view* w, int n, HostWeights* host_w);
 
 }  // namespace tv

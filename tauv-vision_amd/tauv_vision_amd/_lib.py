@@ -138,6 +138,9 @@ EXPORTS = {
     "tv_diag_conv_burst": ([c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32,
                             c_vp], c_i32),
     "tv_diag_burst_plan": ([ctypes.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32)], c_i32),
+    "tv_diag_pack_op": ([ctypes.POINTER(ModelDesc), ctypes.POINTER(WeightView), c_i32, ctypes.c_char_p, c_i32,
+                         ctypes.POINTER(c_i32), ctypes.c_char_p, c_i32, ctypes.POINTER(c_i32 * 6), c_i32,
+                         ctypes.POINTER(c_i64), c_vp, c_vp, c_vp, ctypes.POINTER(c_i64)], c_i32),
     "tv_diag_maxpool3x3s2": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp], c_i32),
     "tv_diag_add_relu": ([c_vp, c_vp, c_vp, c_i64, c_i32, c_vp], c_i32),
     "tv_diag_maxpool2": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp], c_i32),

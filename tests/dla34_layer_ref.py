@@ -24,7 +24,7 @@ Layer kinds and where their bounds come from:
                 pad (3, 0)) and the level0 / level1 convs (C = 16, 32);
               * BasicBlock `conv2+residual`: the residual is a second K-segment, Tree.project's 1x1 + BN
                 folded over the max-pooled bottom (r_seg = 1), or an identity segment whose stored
-                weight is exactly 1 (Engine::pack_op `sg.identity`: r_seg = 0, nothing in Q);
+                weight is exactly 1 (pack_op_host `sg.identity`: r_seg = 0, nothing in Q);
               * the Root 1x1 over torch.cat(children): one K-segment per child in the reference's order
                 (x2, x1, *children), segment j reading input channels [ci0_j, ci0_j + C_j) of the one
                 `root.conv.weight` (level 3: 128 + 128 + 64 + 128, level 5: 512 + 512 + 256);
@@ -83,7 +83,7 @@ Layer kinds and where their bounds come from:
               a 16-bit dtype); the GEMM is a plain 1x1 conv over the stored columns (r = 0 in fp32).
               Fused (dcn.hip: DcnInFused / DcnFused): the OP_DCN row is reported as not stored and the
               GEMM row carries both. The sampled column is rounded to the compute dtype before the MFMA
-              ("one rounding to T") and the weights are rounded (pack_op): r = 2 on A = sum |col| |w|,
+              ("one rounding to T") and the weights are rounded (pack_op_host): r = 2 on A = sum |col| |w|,
               and the sampling error passes through the weights: S = sum |w| dcol. Split-K partials are
               fp32 sums of the same products (any order: the K 2^-24 term).
                 det = (2 u (1 + u) + K 2^-24) (A + S) + S + u |ref| + ETA,   K = 9 C

@@ -243,7 +243,7 @@ def emulate(layer, xs, precision, weight_fault=None):
     dt = TORCH_DTYPE[precision]
     segs = []
     for i, (src, w, stride, pad) in enumerate(layer.segs):
-        wr = w.float().to(dt).float()  # (Engine::pack_op: folded in double, staged as fp32, stored as dt)
+        wr = w.float().to(dt).float()  # (pack_op_host: folded in double, staged as fp32, stored as dt)
         segs.append((src, wr if weight_fault is None else weight_fault(i, wr), stride, pad))
     low = Layer(layer.label, layer.kind, segs, layer.bias.float(), layer.act, layer.skip, layer.out_f32, layer.K)
     y = evaluate(low, {k: v.float() for k, v in xs.items() if k in layer.sources()})

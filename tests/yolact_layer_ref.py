@@ -22,11 +22,11 @@ Every rounding to the compute dtype is within max(u |x|, ETA) of x, ETA half the
 Layer kinds and where their bounds come from (the kernel's text is named per kind):
 
  conv         layer_ref's conv, with three extensions.
-              * identity K-segments (Engine::pack_op, `sg.identity`): the residual x enters the GEMM as
+              * identity K-segments (pack_op_host, `sg.identity`): the residual x enters the GEMM as
                 a 1x1 segment whose weight is the unit matrix. Plain (ResNet `conv2 + bn2 + x`, the
                 head Bottleneck's `conv3 + x`): the stored weight is exactly 1 in every dtype, the
                 product x * 1 is exact: r_seg = 0, and the segment adds nothing to Q. Through an eval
-                BatchNorm (the head block's last GEMM): pack_op stores `(float)scale[co]` rounded to
+                BatchNorm (the head block's last GEMM): pack_op_host stores `(float)scale[co]` rounded to
                 the compute dtype on the diagonal and adds the shift to the fp32 bias: a weight like
                 any other, r_seg = 1. Either way the segment's cin products are part of K and A (the
                 kernel does run the k-steps, over zeros off the diagonal).
@@ -36,7 +36,7 @@ Layer kinds and where their bounds come from (the kernel's text is named per kin
                 accumulator is stored, no u |ref| term. The stacked conv has zero weight rows and zero
                 bias up to a multiple of 4 columns (planner_yolact_head.cpp final_conv): the graph
                 carries them, so the padding columns must come out as exact zeros.
-              fp32: pack_op stores the fp32 weights it folded, the operands are exact: r_seg = 0 and
+              fp32: pack_op_host stores the fp32 weights it folded, the operands are exact: r_seg = 0 and
               the bound is K 2^-24 A + 2^-24 |ref|.
  stage        the ResNet input staging (aux.hip prep_nchw): pixel (y, x) holds the 7 x 3 values
               img[c, y, x + kx - 3] (zero outside the row) at channel 3 kx + c, zeros in channels

@@ -3,7 +3,7 @@
 The engine's reduced-precision numerics, restated op for op on the CPU (this file is measurement
 infrastructure and imports the oracle; nothing in the product path uses it):
   * BatchNorm folded into the conv weights in double, the folded weights rounded to the compute
-    dtype, the folded bias kept fp32 (engine.cpp pack_op);
+    dtype, the folded bias kept fp32 (pack.cpp pack_op_host);
   * activations stored in the compute dtype: the normalised input (stem LUT), every conv output
     after its activation, every ConvTranspose + pad_to_match + skip sum (convt.hip: one rounding
     of (acc + bias) + skip);
