@@ -532,6 +532,67 @@ int tv_centernet_loss_finalize(const tv_loss_desc* desc, const void* workspace, 
  * n < 0, an unknown dtype. */
 int tv_centernet_loss_scale(void* grad, int32_t dtype, int64_t n, const float* scale, void* stream);
 
+/* The YOLACT training loss (yolact/model/loss.py:8-124) with its gradients, in seven launches on `stream`
+ * whatever B, T and the number of positive anchors. One description serves every call. Calls, in order:
+ * tv_yolact_loss_match: per (sample, anchor) iou_matrix (boxes.py:64-85, the same fp32 operation
+ *   sequence, no contraction) times truth_valid, the max over T (lowest truth index wins ties), positive =
+ *   iou >= iou_pos_threshold, negative = iou <= iou_neg_threshold (a NaN IoU is neither) into match_index /
+ *   positive / negative, and the background softmax probability, the mining key, into `workspace`.
+ * tv_yolact_loss_select: per sample the positives in anchor order into a list, k = min(
+ *   negative_example_ratio * n_positive, n_negative), the exact k negatives of smallest background
+ *   probability (lowest anchor index wins ties); selected = positive | mined.
+ * tv_yolact_loss_anchors: cross-entropy (log-softmax) at the selected anchors against the matched truth's
+ *   class at positives and 0 elsewhere; smooth-L1 (beta 1) of box_encoding against box_encode(
+ *   truth_box[match], anchor) (boxes.py:45-52) at positives. Writes softmax - onehot / the smooth-L1
+ *   derivative into the gradient buffers, zeros elsewhere, and the zero rows of d mask_coeff.
+ * tv_yolact_loss_mask_sums: per (sample, truth index t) the sum of (truth_seg_map == t) resized to h x w by
+ *   upsample_bilinear2d (align_corners false).
+ * tv_yolact_loss_mask: per positive, sigmoid(sum_p coeff_p proto_p) clamped to [1e-4, 1 - 1e-4], BCE against
+ *   the resized truth mask (clamped alike), weighted by box_to_mask(truth_box[match]) (boxes.py:88-103) times
+ *   truth_img_valid resized by upsample_nearest2d, divided by the resized mask's sum; positives whose sum
+ *   is 0 are skipped. Writes d mask_prototype (every element once).
+ * tv_yolact_loss_mask_coeff: the positives' rows of d mask_coeff. Needs gradient buffers (else TV_EINVAL).
+ * tv_yolact_loss_finalize: out[0..3] = total, classification, box, mask (each sum divided by (1 + ratio) *
+ *   n_positive resp. n_positive over the batch, or left as it is without a positive); out[4..6] = the
+ *   batch's positive, negative and selected counts; out[8..11] = the factor that scales the stored gradient
+ *   of classification, box_encoding, mask_coeff, mask_prototype; the rest of out[0..15] is 0.
+ * Prediction tensors are fp32 with element strides (classification [B,A,C], box_encoding [B,A,4],
+ * mask_coeff [B,A,P], anchor [A,4], mask_prototype [B,P,h,w]); the gradient buffers (all four or none) have
+ * strides of their own and receive unscaled gradients (tv_centernet_loss_scale applies the factors). The
+ * truth is contiguous: truth_valid u8 [B,T], truth_classification int64 [B,T] (in [0, C) where valid:
+ * the caller checks), truth_box fp32 [B,T,4], truth_seg_map [B,in_h,in_w] of seg_itemsize bytes (1: uint8;
+ * 2, 4, 8: signed), truth_img_valid u8 [B,in_h,in_w]. match_index int32 [B,A], positive / negative /
+ * selected u8 [B,A] are outputs.
+ * TV_EINVAL before any launch, with nothing written: a null description, pointer or workspace, B, A, C, P
+ * or T < 1, an empty grid, negative_example_ratio < 0, a negative stride, some but not all gradient
+ * buffers, or a workspace smaller than tv_yolact_loss_workspace_size. */
+typedef struct tv_yolact_loss_desc {
+  int32_t B, A, C, P, T, h, w, in_h, in_w, seg_itemsize, negative_example_ratio, reserved;
+  double iou_pos_threshold, iou_neg_threshold, box_variances[2];
+  const void *classification, *box_encoding, *mask_coeff, *anchor, *mask_prototype;
+  void *grad_classification, *grad_box_encoding, *grad_mask_coeff, *grad_mask_prototype;
+  const uint8_t* truth_valid;
+  const int64_t* truth_classification;
+  const float* truth_box;
+  const void* truth_seg_map;
+  const uint8_t* truth_img_valid;
+  int32_t* match_index;
+  uint8_t *positive, *negative, *selected;
+  int64_t classification_stride[3], box_encoding_stride[3], mask_coeff_stride[3], anchor_stride[2];
+  int64_t mask_prototype_stride[4];
+  int64_t grad_classification_stride[3], grad_box_encoding_stride[3], grad_mask_coeff_stride[3];
+  int64_t grad_mask_prototype_stride[4];
+} tv_yolact_loss_desc;
+int tv_yolact_loss_workspace_size(const tv_yolact_loss_desc* desc, int64_t* bytes);
+int tv_yolact_loss_match(const tv_yolact_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream);
+int tv_yolact_loss_select(const tv_yolact_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream);
+int tv_yolact_loss_anchors(const tv_yolact_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream);
+int tv_yolact_loss_mask_sums(const tv_yolact_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream);
+int tv_yolact_loss_mask(const tv_yolact_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream);
+int tv_yolact_loss_mask_coeff(const tv_yolact_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream);
+int tv_yolact_loss_finalize(const tv_yolact_loss_desc* desc, void* workspace, int64_t workspace_bytes, float* out,
+                            void* stream);
+
 /* Diagnostics (GPU tests): one DeformConv2d(x, offset, sigmoid(mask)) (DeformConv.forward,
  * centerpoint_dla.py:389-391: 3x3, stride 1, pad 1) + bias + activation (0 none, 1 ReLU, 2 leaky)
  * through the kernel the engine uses for DLA-34's DeformConv layers. x: compute-dtype NHWC

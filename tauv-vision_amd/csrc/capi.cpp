@@ -701,4 +701,56 @@ int tv_centernet_loss_scale(void* grad, int32_t dtype, int64_t n, const float* s
   TV_GUARD({ return tv::launch_centernet_loss_scale(grad, dtype, n, scale, (hipStream_t)stream); })
 }
 
+int tv_yolact_loss_workspace_size(const tv_yolact_loss_desc* desc, int64_t* bytes) {
+  TV_GUARD({
+    long long n = 0;
+    const int rc = tv::yolact_loss_workspace_size(desc, bytes ? &n : nullptr);
+    if (rc == TV_OK) *bytes = n;
+    return rc;
+  })
+}
+
+int tv_yolact_loss_match(const tv_yolact_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream) {
+  TV_GUARD({
+    return tv::launch_yolact_loss(tv::TV_YOLACT_LOSS_MATCH, desc, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
+  })
+}
+
+int tv_yolact_loss_select(const tv_yolact_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream) {
+  TV_GUARD({
+    return tv::launch_yolact_loss(tv::TV_YOLACT_LOSS_SELECT, desc, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
+  })
+}
+
+int tv_yolact_loss_anchors(const tv_yolact_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream) {
+  TV_GUARD({
+    return tv::launch_yolact_loss(tv::TV_YOLACT_LOSS_ANCHORS, desc, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
+  })
+}
+
+int tv_yolact_loss_mask_sums(const tv_yolact_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream) {
+  TV_GUARD({
+    return tv::launch_yolact_loss(tv::TV_YOLACT_LOSS_MASK_SUMS, desc, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
+  })
+}
+
+int tv_yolact_loss_mask(const tv_yolact_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream) {
+  TV_GUARD({
+    return tv::launch_yolact_loss(tv::TV_YOLACT_LOSS_MASK, desc, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
+  })
+}
+
+int tv_yolact_loss_mask_coeff(const tv_yolact_loss_desc* desc, void* workspace, int64_t workspace_bytes, void* stream) {
+  TV_GUARD({
+    return tv::launch_yolact_loss(tv::TV_YOLACT_LOSS_MASK_COEFF, desc, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
+  })
+}
+
+int tv_yolact_loss_finalize(const tv_yolact_loss_desc* desc, void* workspace, int64_t workspace_bytes, float* out,
+                            void* stream) {
+  TV_GUARD({
+    return tv::launch_yolact_loss(tv::TV_YOLACT_LOSS_FINALIZE, desc, workspace, workspace_bytes, out, (hipStream_t)stream);
+  })
+}
+
 }  // extern "C"

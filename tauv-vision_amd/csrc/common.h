@@ -250,6 +250,7 @@ int launch_train_keypoints(const uint8_t* kvalid, const long long* klabel, const
                            double heat_sigma, double aff_sigma, float* heat, float* aw, float* aff, hipStream_t s);
 }  // namespace tv
 struct tv_loss_desc;
+struct tv_yolact_loss_desc;
 namespace tv {
 // loss.hip: the CenterNet loss with its gradients (loss.py:178-390); the contracts are
 // tv_centernet_loss_*' in include/tauv_vision_amd.h. Arguments are checked here (return 1 = TV_EINVAL).
@@ -259,6 +260,11 @@ int launch_centernet_loss_objects(const tv_loss_desc* d, void* ws, long long ws_
 int launch_centernet_loss_finalize(const tv_loss_desc* d, const void* ws, long long ws_bytes, float* out,
                                    hipStream_t s);
 int launch_centernet_loss_scale(void* grad, int dtype, long long n, const float* scale, hipStream_t s);
+// yolact_loss.hip: the launches of tv_yolact_loss_* (the header states them), one per stage
+enum { TV_YOLACT_LOSS_MATCH = 0, TV_YOLACT_LOSS_SELECT, TV_YOLACT_LOSS_ANCHORS, TV_YOLACT_LOSS_MASK_SUMS,
+       TV_YOLACT_LOSS_MASK, TV_YOLACT_LOSS_MASK_COEFF, TV_YOLACT_LOSS_FINALIZE };
+int yolact_loss_workspace_size(const tv_yolact_loss_desc* d, long long* bytes);
+int launch_yolact_loss(int stage, const tv_yolact_loss_desc* d, void* ws, long long ws_bytes, float* out, hipStream_t s);
 // diag.cpp: one DeformConv2d + bias + activation through a chosen DCN kernel (GPU tests)
 int diag_dcn_conv(const void* x, const void* om, int B, int H, int W, int C, int om_ldc, const float* weight,
                   const float* bias, int N, int act, int dtype, int variant, void* out, hipStream_t s);

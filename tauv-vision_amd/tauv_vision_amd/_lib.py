@@ -50,6 +50,24 @@ class LossDesc(ctypes.Structure):
                                     "angle_range")]
 
 
+class YolactLossDesc(ctypes.Structure):
+    """tv_yolact_loss_desc (include/tauv_vision_amd.h)."""
+    _fields_ = [(n, c_i32) for n in ("B", "A", "C", "P", "T", "h", "w", "in_h", "in_w", "seg_itemsize",
+                                     "negative_example_ratio", "reserved")] + \
+               [("iou_pos_threshold", c_f64), ("iou_neg_threshold", c_f64), ("box_variances", c_f64 * 2)] + \
+               [(n, c_vp) for n in ("classification", "box_encoding", "mask_coeff", "anchor", "mask_prototype",
+                                    "grad_classification", "grad_box_encoding", "grad_mask_coeff",
+                                    "grad_mask_prototype", "truth_valid", "truth_classification", "truth_box",
+                                    "truth_seg_map", "truth_img_valid", "match_index", "positive", "negative",
+                                    "selected")] + \
+               [("classification_stride", c_i64 * 3), ("box_encoding_stride", c_i64 * 3),
+                ("mask_coeff_stride", c_i64 * 3), ("anchor_stride", c_i64 * 2), ("mask_prototype_stride", c_i64 * 4),
+                ("grad_classification_stride", c_i64 * 3), ("grad_box_encoding_stride", c_i64 * 3),
+                ("grad_mask_coeff_stride", c_i64 * 3), ("grad_mask_prototype_stride", c_i64 * 4)]
+
+
+YOLACT_LOSS_STAGES = ("match", "select", "anchors", "mask_sums", "mask", "mask_coeff")  # then finalize
+
 EXPORTS = {
     "tv_model_param_count": ([ctypes.POINTER(ModelDesc), ctypes.POINTER(c_i32)], c_i32),
     "tv_model_param_info": ([ctypes.POINTER(ModelDesc), c_i32, ctypes.c_char_p, c_i32, ctypes.POINTER(c_i64),
@@ -128,6 +146,9 @@ EXPORTS = {
     "tv_centernet_loss_objects": ([ctypes.POINTER(LossDesc), c_vp, c_i64, c_vp], c_i32),
     "tv_centernet_loss_finalize": ([ctypes.POINTER(LossDesc), c_vp, c_i64, c_vp, c_vp], c_i32),
     "tv_centernet_loss_scale": ([c_vp, c_i32, c_i64, c_vp, c_vp], c_i32),
+    "tv_yolact_loss_workspace_size": ([ctypes.POINTER(YolactLossDesc), ctypes.POINTER(c_i64)], c_i32),
+    **{"tv_yolact_loss_" + n: ([ctypes.POINTER(YolactLossDesc), c_vp, c_i64, c_vp], c_i32) for n in YOLACT_LOSS_STAGES},
+    "tv_yolact_loss_finalize": ([ctypes.POINTER(YolactLossDesc), c_vp, c_i64, c_vp, c_vp], c_i32),
     "tv_diag_dcn_conv": ([c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32,
                           c_vp, c_vp], c_i32),
     "tv_diag_conv_small": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
