@@ -9,36 +9,19 @@
 //        * ConvTranspose2d(k=s) + pad_to_match + add -> one phase-scatter GEMM (+ margin copy)
 //        * all heads' 3x3 convs                    -> one GEMM (N = heads * 2C), LeakyReLU
 //        * all heads' 1x1 convs                    -> one block-diagonal GEMM, fp32 output
-#include "planner.h"
-
 #include <algorithm>
-#include <functional>
 
-#include "common.h"
+#include "plan_builder.h"
 
 namespace tv {
 namespace {
 
-
-struct Walker {
+struct Walker : PlanBuilder {
   const tv_model_desc& d;
-  Plan& P;
-  explicit Walker(const tv_model_desc& desc, Plan& plan) : d(desc), P(plan) {}
+  Walker(const tv_model_desc& desc, Plan& plan) : PlanBuilder{plan}, d(desc) {}
   bool backbone_only() const { return d.arch == TV_ARCH_CENTERNET_BACKBONE; }
 
   // ---------------- (1) parameters ----------------
-  void add(const std::string& n, std::vector<int64_t> s) { P.params.push_back({n, std::move(s)}); }
-  void conv_p(const std::string& p, int cout, int cin, int k) {
-    add(p + ".weight", {cout, cin, k, k});
-    add(p + ".bias", {cout});
-  }
-  void bn_p(const std::string& p, int c) {
-    add(p + ".weight", {c});
-    add(p + ".bias", {c});
-    add(p + ".running_mean", {c});
-    add(p + ".running_var", {c});
-    add(p + ".num_batches_tracked", {});
-  }
   void block_p(const std::string& p, int cin, int cout) {
     conv_p(p + ".conv1", cout, cin, 3);
     bn_p(p + ".bn1", cout);
@@ -103,35 +86,6 @@ struct Walker {
   }
 
   // ---------------- (2) forward lowering ----------------
-  int tensor(int H, int W, int C) {
-    P.tensors.push_back({H, W, C});
-    return (int)P.tensors.size() - 1;
-  }
-  static int out_dim(int x, int k, int s, int pad) { return (x + 2 * pad - k) / s + 1; }
-
-  int conv(const std::string& label, std::vector<SegSpec> segs, int N, int act) {
-    const TensorSpec& s0 = P.tensors[segs[0].src];
-    int Ho = out_dim(s0.H, segs[0].kh, segs[0].stride, segs[0].pad);
-    int Wo = out_dim(s0.W, segs[0].kw, segs[0].stride, segs[0].pad_w >= 0 ? segs[0].pad_w : segs[0].pad);
-    OpSpec op;
-    op.kind = OP_CONV;
-    op.label = label;
-    op.N = N;
-    op.act = act;
-    for (auto& sg : segs) {
-      const TensorSpec& t = P.tensors[sg.src];
-      op.flops += 2.0 * Ho * Wo * N * (double)(sg.kh * (sg.row_expand ? sg.row_expand : sg.kw) * sg.cin);
-      (void)t;
-    }
-    op.segs = std::move(segs);
-    op.out = tensor(Ho, Wo, N);
-    P.ops.push_back(op);
-    return op.out;
-  }
-  SegSpec seg(int src, const std::string& conv_prefix, const std::string& bn, int ci0, int cin, int k, int stride,
-              int pad) {
-    return SegSpec{src, conv_prefix, bn, ci0, cin, k, k, stride, pad};
-  }
   int conv_bn_relu(const std::string& conv_p, const std::string& bn, int x, int cin, int cout, int k, int stride,
                    int pad) {
     return conv(conv_p, {seg(x, conv_p, bn, 0, cin, k, stride, pad)}, cout, 1);
@@ -198,9 +152,7 @@ struct Walker {
     op.cov_x0 = op.sx;
     op.cov_x1 = std::min(tgt.W, op.sx + wu);
     op.flops = 2.0 * src.H * src.W * (double)(s * s * c) * c;
-    op.out = tensor(tgt.H, tgt.W, c);
-    P.ops.push_back(op);
-    const int u = op.out;
+    const int u = emit(op, tgt.H, tgt.W, c);
     return conv_bn_relu(p + ".output_layers." + js + ".0", p + ".output_layers." + js + ".1", u, c, c, 3, 1, 1);
   }
   std::vector<int> ida_up(const std::string& p, const std::vector<int>& feats) {
@@ -217,27 +169,10 @@ struct Walker {
   int forward() {
     const int L = d.n_levels;
     std::vector<int> ch(d.channels, d.channels + L + 1);
-    // input staged row-expanded for the 7x7 stem: pixel (y, x) holds the 7 horizontal taps
-    // x-3..x+3 of its 3 channels (21 values, zero-padded to a whole 16-byte chunk), so the
-    // stem is a 7x1 conv with K = 7 * 24 instead of 49 taps of a padded pixel
-    const int vec = 16 / dtype_size(d.compute_dtype);
-    const int cpad = (7 * 3 + vec - 1) / vec * vec;
-    P.in_cpad = cpad;
-    int img = tensor(d.in_h, d.in_w, cpad);
-    {
-      OpSpec op;
-      op.kind = OP_PREP;
-      op.label = "input staging (NCHW fp32 / u8 frames -> NHWC)";
-      op.out = img;
-      op.N = cpad;
-      P.ops.push_back(op);
-    }
+    const int img = staged_image(d, "input staging (NCHW fp32 / u8 frames -> NHWC)");
     const std::string dd = "backbone.dla_down";
-    SegSpec stem = seg(img, dd + ".projection_layer.0", dd + ".projection_layer.1", 0, 3, 7, 1, 3);
-    stem.kw = 1;
-    stem.pad_w = 0;
-    stem.row_expand = 7;
-    int x = conv(dd + ".projection_layer.0", {stem}, ch[0], 1);
+    int x = conv(dd + ".projection_layer.0", {stem7(img, dd + ".projection_layer.0", dd + ".projection_layer.1", 1)},
+                 ch[0], 1);
     for (int i = 0; i < d.downsamples; ++i) x = block(dd + ".block_layers." + std::to_string(i), x, ch[0], ch[0], 2);
     std::vector<int> feats{x};
     for (int i = 0; i < L; ++i) {
@@ -256,65 +191,12 @@ struct Walker {
       cur = up_add("backbone.ida_up_reverse", i, collected[i + 1], cur, 1 << (i + 1));
       if (cur < 0) return 2;
     }
-    const int C = ch[0];
-    if (backbone_only()) {
-      // DLABackbone.forward's result (dla.py:409-416) into the caller's fp32 NHWC buffer: an
-      // identity 1x1 GEMM (exact: one product per output, fp32 accumulation)
-      const TensorSpec ft = P.tensors[cur];
-      OpSpec o;
-      o.kind = OP_CONV;
-      o.label = "backbone output -> fp32 NHWC";
-      SegSpec sg{cur, "", "", 0, C, 1, 1, 1, 0};
-      sg.identity = true;
-      o.segs = {sg};
-      o.N = C;
-      o.act = 0;
-      o.out = -1;
-      P.out_c = C;
-      P.out_cpad = C;
-      P.out_h = ft.H;
-      P.out_w = ft.W;
-      P.ops.push_back(o);
-      for (auto& op : P.ops) P.flops_per_frame += op.flops;
-      return 0;
-    }
-    // heads: stacked 3x3 (C -> 2C each) + LeakyReLU, then block-diagonal 1x1 to fp32 output
-    OpSpec h1;
-    h1.kind = OP_CONV;
-    h1.label = "heads.*.0 (stacked) + LeakyReLU";
-    h1.segs = {SegSpec{cur, "", "", 0, C, 3, 3, 1, 1}};
-    h1.N = 2 * C * d.n_heads;
-    h1.act = 2;
-    for (int h = 0; h < d.n_heads; ++h) {
-      h1.stack_w.push_back("heads." + std::to_string(h) + ".0");
-      h1.stack_n.push_back(2 * C);
-    }
-    const TensorSpec ft = P.tensors[cur];
-    h1.flops = 2.0 * ft.H * ft.W * h1.N * 9.0 * C;
-    h1.out = tensor(ft.H, ft.W, h1.N);
-    P.ops.push_back(h1);
-    OpSpec h2;
-    h2.kind = OP_CONV;
-    h2.label = "heads.*.2 (block-diagonal) -> fp32 NHWC";
-    h2.segs = {SegSpec{h1.out, "", "", 0, h1.N, 1, 1, 1, 0}};
-    int ctot = 0;
-    for (int h = 0; h < d.n_heads; ++h) {
-      h2.stack_w.push_back("heads." + std::to_string(h) + ".2");
-      h2.stack_n.push_back(d.head_channels[h]);
-      h2.diag_in_off.push_back(2 * C * h);
-      h2.diag_out_off.push_back(ctot);
-      h2.flops += 2.0 * ft.H * ft.W * d.head_channels[h] * 2.0 * C;
-      ctot += d.head_channels[h];
-    }
-    P.out_c = ctot;
-    P.out_cpad = (ctot + 3) / 4 * 4;
-    P.out_h = ft.H;
-    P.out_w = ft.W;
-    h2.N = P.out_cpad;
-    h2.act = 0;
-    h2.out = -1;
-    P.ops.push_back(h2);
-    for (auto& op : P.ops) P.flops_per_frame += op.flops;
+    // DLABackbone.forward's result (dla.py:409-416) as it is, or through the heads: stacked 3x3
+    // (C -> 2C each) + LeakyReLU, then block-diagonal 1x1
+    single_output(backbone_only() ? to_caller_f32(cur, 0, "backbone output -> fp32 NHWC")
+                                  : stacked_heads(cur, "heads.", d.n_heads, d.head_channels, 2 * ch[0], 2,
+                                                  "heads.*.0 (stacked) + LeakyReLU",
+                                                  "heads.*.2 (block-diagonal) -> fp32 NHWC"));
     return 0;
   }
 };
@@ -328,6 +210,7 @@ int build_plan(const tv_model_desc& d0, Plan* plan) {
   tv_model_desc d = d0;
   if (d.compute_dtype == TV_F32X3) d.compute_dtype = TV_F32;
   int rc = build_plan_arch(d, plan);
+  if (!rc) rc = PlanBuilder{*plan}.finish();  // every planner's one exit
   if (rc) return rc;
   // the single-input single-output archs: their one input frame and output tensor
   if (plan->ins.empty()) plan->ins.push_back(IoSpec{d.in_h, d.in_w, plan->in_channels, plan->in_channels});
@@ -370,15 +253,7 @@ static int build_plan_arch(const tv_model_desc& d, Plan* plan) {
   *plan = Plan();
   Walker w(d, *plan);
   w.params();
-  for (const ParamInfo& p : plan->params) plan->names.insert(p.name);
-  int rc = w.forward();
-  if (rc) return rc;
-  for (auto& op : plan->ops)
-    if (op.kind == OP_CONV && op.segs.size() > (size_t)kMaxSeg) {
-      set_error("too many concatenated inputs for one Root (tree height too large)");
-      return TV_ESHAPE;
-    }
-  return TV_OK;
+  return w.forward();
 }
 
 }  // namespace tv

@@ -1,6 +1,9 @@
-// Network planner for the reference "R18" CenterNet (Centernet + DLABackbone):
-// enumerates the reference state_dict layout and lowers the forward pass to a list of
-// fused GEMM launches over NHWC tensors.
+// The network planners' common output, a Plan: the reference state_dict layout of a model desc
+// (parameters in registration order) and its forward pass lowered to a list of ops over NHWC
+// tensors, fused GEMMs for the most part. One planner per network: the "R18" CenterNet (planner.cpp),
+// CenterpointDLA34 (planner_dla34.cpp), and YOLACT's ResNet-18 backbone, neck + head and protonet
+// (planner_resnet.cpp, planner_yolact_head.cpp, planner_protonet.cpp); all of them build their plan
+// with plan_builder.h.
 #pragma once
 #include <cstdint>
 #include <set>
@@ -66,12 +69,12 @@ struct ScatterPart {
 };
 
 struct OpSpec {
-  int kind;
+  int kind = OP_CONV;
   std::string label;          // human-readable (reference module path)
   std::vector<SegSpec> segs;  // OP_CONV
-  int out;                    // tensor id (-1 = the caller's fp32 output buffer)
-  int N;                      // output channels (GEMM columns before phase expansion)
-  int act;                    // 0 none, 1 relu, 2 leaky
+  int out = -1;               // tensor id (-1 - i = the caller's fp32 output buffer i)
+  int N = 0;                  // output channels (GEMM columns before phase expansion)
+  int act = 0;                // 0 none, 1 relu, 2 leaky
   // head fusion: weights of several convs stacked along N (names in order, N each)
   std::vector<std::string> stack_w;
   std::vector<int> stack_n;

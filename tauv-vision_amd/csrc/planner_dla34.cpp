@@ -20,8 +20,7 @@
 #include <algorithm>
 #include <map>
 
-#include "common.h"
-#include "planner.h"
+#include "plan_builder.h"
 
 namespace tv {
 namespace {
@@ -31,26 +30,15 @@ constexpr int kChannels[6] = {16, 32, 64, 128, 256, 512};
 constexpr int kHeadConv = 256;                       // get_pose_net head_conv, :534-541
 constexpr int kFirstLevel = 2, kLastLevel = 5;       // down_ratio 4, last_level 5
 
-struct DlaWalker {
+struct DlaWalker : PlanBuilder {
   const tv_model_desc& d;
-  Plan& P;
   std::map<int, int> pooled;  // tensor -> its max-pooled tensor (shared by tree1 and the Root)
-  DlaWalker(const tv_model_desc& desc, Plan& plan) : d(desc), P(plan) {}
+  // identity_flops off: a BasicBlock's residual added as it is counts no FLOPs in this network
+  DlaWalker(const tv_model_desc& desc, Plan& plan) : PlanBuilder{plan, "", false}, d(desc) {}
 
   // ---------------- (1) parameters ----------------
-  void add(const std::string& n, std::vector<int64_t> s) { P.params.push_back({n, std::move(s)}); }
-  void conv_w(const std::string& p, int cout, int cin, int k) { add(p + ".weight", {cout, cin, k, k}); }
-  void conv_wb(const std::string& p, int cout, int cin, int k) {
-    conv_w(p, cout, cin, k);
-    add(p + ".bias", {cout});
-  }
-  void bn_p(const std::string& p, int c) {
-    add(p + ".weight", {c});
-    add(p + ".bias", {c});
-    add(p + ".running_mean", {c});
-    add(p + ".running_var", {c});
-    add(p + ".num_batches_tracked", {});
-  }
+  void conv_w(const std::string& p, int cout, int cin, int k) { conv_p(p, cout, cin, k, false); }  // bias=False
+  void conv_wb(const std::string& p, int cout, int cin, int k) { conv_p(p, cout, cin, k); }
   void basic_p(const std::string& p, int cin, int cout) {
     conv_w(p + ".conv1", cout, cin, 3);
     bn_p(p + ".bn1", cout);
@@ -145,31 +133,6 @@ struct DlaWalker {
   }
 
   // ---------------- (2) forward lowering ----------------
-  int tensor(int H, int W, int C) {
-    P.tensors.push_back({H, W, C});
-    return (int)P.tensors.size() - 1;
-  }
-  static int out_dim(int x, int k, int s, int pad) { return (x + 2 * pad - k) / s + 1; }
-  static SegSpec seg(int src, const std::string& w, const std::string& bn, int ci0, int cin, int k, int stride,
-                     int pad) {
-    return SegSpec{src, w, bn, ci0, cin, k, k, stride, pad};
-  }
-  int conv(const std::string& label, std::vector<SegSpec> segs, int N, int act) {
-    const TensorSpec s0 = P.tensors[segs[0].src];
-    const int Ho = out_dim(s0.H, segs[0].kh, segs[0].stride, segs[0].pad);
-    const int Wo = out_dim(s0.W, segs[0].kw, segs[0].stride, segs[0].pad_w >= 0 ? segs[0].pad_w : segs[0].pad);
-    OpSpec op;
-    op.kind = OP_CONV;
-    op.label = label;
-    op.N = N;
-    op.act = act;
-    for (auto& sg : segs)
-      if (!sg.identity) op.flops += 2.0 * Ho * Wo * N * (double)(sg.kh * (sg.row_expand ? sg.row_expand : sg.kw) * sg.cin);
-    op.segs = std::move(segs);
-    op.out = tensor(Ho, Wo, N);
-    P.ops.push_back(op);
-    return op.out;
-  }
   int maxpool(int x) {
     auto it = pooled.find(x);
     if (it != pooled.end()) return it->second;
@@ -179,10 +142,7 @@ struct DlaWalker {
     op.label = "MaxPool2d(2, 2, ceil_mode=True)";
     op.src = x;
     op.N = t.C;
-    op.out = tensor((t.H + 1) / 2, (t.W + 1) / 2, t.C);
-    P.ops.push_back(op);
-    pooled[x] = op.out;
-    return op.out;
+    return pooled[x] = emit(op, (t.H + 1) / 2, (t.W + 1) / 2, t.C);
   }
   // BasicBlock (:30-59) with its residual as the second K-segment of conv2
   int basic(const std::string& p, int x, int cin, int cout, int stride, SegSpec res) {
@@ -193,11 +153,6 @@ struct DlaWalker {
       return -1;
     }
     return conv(p + ".conv2+residual", {seg(t, p + ".conv2", p + ".bn2", 0, cout, 3, 1, 1), res}, cout, 1);
-  }
-  static SegSpec identity(int x, int c) {
-    SegSpec s = seg(x, "", "", 0, c, 1, 1, 0);
-    s.identity = true;
-    return s;
   }
   int root(const std::string& p, const std::vector<int>& kids, int cout) {
     std::vector<SegSpec> segs;
@@ -233,26 +188,14 @@ struct DlaWalker {
   // DeformConv.forward (:386-392)
   int deform(const std::string& p, int x, int cho) {
     const TensorSpec t = P.tensors[x];
-    OpSpec om;
-    om.kind = OP_CONV;
-    om.label = p + ".offset+mask";
-    om.segs = {seg(x, "", "", 0, t.C, 3, 1, 1)};
-    om.N = 32;  // 18 offsets (dy, dx per tap) + 9 mask logits + 5 zero columns
-    om.act = 0;
-    om.stack_w = {p + ".offset", p + ".mask"};
-    om.stack_n = {18, 9};
-    om.flops = 2.0 * t.H * t.W * 27 * 9.0 * t.C;
-    om.out = tensor(t.H, t.W, 32);
-    P.ops.push_back(om);
     OpSpec dc;
     dc.kind = OP_DCN;
     dc.label = p + ".conv (DCNv2 sampling)";
     dc.src = x;
-    dc.add = om.out;
+    // N = 32: 18 offsets (dy, dx per tap) + 9 mask logits + 5 zero columns
+    dc.add = stacked_conv3x3(p + ".offset+mask", x, {p + ".offset", p + ".mask"}, {18, 9}, 32, 0);
     dc.N = 9 * t.C;
-    dc.out = tensor(t.H, t.W, 9 * t.C);
-    P.ops.push_back(dc);
-    SegSpec cs = seg(dc.out, p + ".conv", p + ".actf.0", 0, t.C, 1, 1, 0);
+    SegSpec cs = seg(emit(dc, t.H, t.W, 9 * t.C), p + ".conv", p + ".actf.0", 0, t.C, 1, 1, 0);
     cs.row_expand = 9;
     return conv(p + ".conv+actf", {cs}, cho, 1);
   }
@@ -282,31 +225,14 @@ struct DlaWalker {
       op.sy = std::max(0, (hu - tgt.H) / 2);  // pad_to_match (:394-407), (W, H) order correct here
       op.sx = std::max(0, (wu - tgt.W) / 2);
       op.flops = 2.0 * src.H * src.W * o * 4.0 * f * f;
-      op.out = tensor(tgt.H, tgt.W, o);
-      P.ops.push_back(op);
-      layers[i] = deform(p + ".node_" + js, op.out, o);
+      layers[i] = deform(p + ".node_" + js, emit(op, tgt.H, tgt.W, o), o);
     }
     return 0;
   }
   int forward() {
-    const int vec = 16 / dtype_size(d.compute_dtype);
-    const int cpad = (7 * 3 + vec - 1) / vec * vec;  // row-expanded 7x7 stem input (planner.cpp)
-    P.in_cpad = cpad;
-    const int img = tensor(d.in_h, d.in_w, cpad);
-    {
-      OpSpec op;
-      op.kind = OP_PREP;
-      op.label = "input staging (NCHW fp32 / u8 frames -> NHWC)";
-      op.out = img;
-      op.N = cpad;
-      P.ops.push_back(op);
-    }
+    const int img = staged_image(d, "input staging (NCHW fp32 / u8 frames -> NHWC)");
     const std::string b = "model.base";
-    SegSpec stem = seg(img, b + ".base_layer.0", b + ".base_layer.1", 0, 3, 7, 1, 3);
-    stem.kw = 1;
-    stem.pad_w = 0;
-    stem.row_expand = 7;
-    int x = conv(b + ".base_layer.0", {stem}, kChannels[0], 1);
+    int x = conv(b + ".base_layer.0", {stem7(img, b + ".base_layer.0", b + ".base_layer.1", 1)}, kChannels[0], 1);
     std::vector<int> layers;
     int cin = kChannels[0];
     for (int l = 0; l < 2; ++l) {  // _make_conv_level (:288-297)
@@ -335,44 +261,8 @@ struct DlaWalker {
     // DLASeg.forward (:515-525)
     std::vector<int> y(out.begin(), out.begin() + (kLastLevel - kFirstLevel));
     if (ida("model.ida_up", y, 0, (int)y.size(), ida_up_def().o)) return TV_ESHAPE;
-    const int cur = y.back();
-    const TensorSpec ft = P.tensors[cur];
-    const int C = ft.C;
-    OpSpec h1;
-    h1.kind = OP_CONV;
-    h1.label = "model.*.0 (stacked heads) + ReLU";
-    h1.segs = {SegSpec{cur, "", "", 0, C, 3, 3, 1, 1}};
-    h1.N = kHeadConv * d.n_heads;
-    h1.act = 1;
-    for (int h = 0; h < d.n_heads; ++h) {
-      h1.stack_w.push_back("model." + std::to_string(h) + ".0");
-      h1.stack_n.push_back(kHeadConv);
-    }
-    h1.flops = 2.0 * ft.H * ft.W * h1.N * 9.0 * C;
-    h1.out = tensor(ft.H, ft.W, h1.N);
-    P.ops.push_back(h1);
-    OpSpec h2;
-    h2.kind = OP_CONV;
-    h2.label = "model.*.2 (block-diagonal) -> fp32 NHWC";
-    h2.segs = {SegSpec{h1.out, "", "", 0, h1.N, 1, 1, 1, 0}};
-    int ctot = 0;
-    for (int h = 0; h < d.n_heads; ++h) {
-      h2.stack_w.push_back("model." + std::to_string(h) + ".2");
-      h2.stack_n.push_back(d.head_channels[h]);
-      h2.diag_in_off.push_back(kHeadConv * h);
-      h2.diag_out_off.push_back(ctot);
-      h2.flops += 2.0 * ft.H * ft.W * d.head_channels[h] * (double)kHeadConv;
-      ctot += d.head_channels[h];
-    }
-    P.out_c = ctot;
-    P.out_cpad = (ctot + 3) / 4 * 4;
-    P.out_h = ft.H;
-    P.out_w = ft.W;
-    h2.N = P.out_cpad;
-    h2.act = 0;
-    h2.out = -1;
-    P.ops.push_back(h2);
-    for (auto& op : P.ops) P.flops_per_frame += op.flops;
+    single_output(stacked_heads(y.back(), "model.", d.n_heads, d.head_channels, kHeadConv, 1,
+                                "model.*.0 (stacked heads) + ReLU", "model.*.2 (block-diagonal) -> fp32 NHWC"));
     return 0;
   }
 };
@@ -396,7 +286,6 @@ int build_plan_dla34(const tv_model_desc& d, Plan* plan) {
   *plan = Plan();
   DlaWalker w(d, *plan);
   w.params();
-  for (const ParamInfo& p : plan->params) plan->names.insert(p.name);
   return w.forward();
 }
 

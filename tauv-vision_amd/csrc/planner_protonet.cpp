@@ -15,50 +15,32 @@
 //          at 4x resolution never reaches HBM
 // append_protonet is (1) and (2) after the input layout op, on any NHWC tensor of a plan: the
 // YOLACT head plan (planner_yolact_head.cpp) runs it on its fpn[0], which then never leaves the arena.
-#include "common.h"
-#include "planner.h"
+#include "plan_builder.h"
 
 namespace tv {
 
 IoSpec append_protonet(Plan& P, const std::string& prefix, int x, int F, int k, int out_slot) {
-  auto add = [&](const std::string& n, std::vector<int64_t> s) { P.params.push_back({prefix + n, std::move(s)}); };
+  PlanBuilder b{P, prefix};
   for (int i = 1; i <= 3; ++i) {
-    add("_layers_" + std::to_string(i) + ".0.0.weight", {F, F, 3, 3});
-    add("_layers_" + std::to_string(i) + ".0.0.bias", {F});
-    if (i < 3) {
-      add("_upsample_layer_" + std::to_string(i) + ".weight", {F, F, 3, 3});
-      add("_upsample_layer_" + std::to_string(i) + ".bias", {F});
-    }
+    b.conv_p("_layers_" + std::to_string(i) + ".0.0", F, F, 3);
+    if (i < 3) b.conv_p("_upsample_layer_" + std::to_string(i), F, F, 3);
   }
-  add("_output_layer.weight", {k, F, 1, 1});
-  add("_output_layer.bias", {k});
+  b.conv_p("_output_layer", k, F, 1);
 
-  auto tensor = [&](int H, int W, int C) {
-    P.tensors.push_back({H, W, C});
-    return (int)P.tensors.size() - 1;
-  };
   auto conv3 = [&](const std::string& name, int src) {
-    const TensorSpec t = P.tensors[src];
-    OpSpec op;
-    op.kind = OP_CONV;
-    op.label = prefix + name + " + LeakyReLU";
-    op.segs = {SegSpec{src, prefix + name, "", 0, F, 3, 3, 1, 1}};
-    op.N = F;
-    op.act = 2;
-    op.flops = 2.0 * t.H * t.W * F * 9.0 * F;
-    op.out = tensor(t.H, t.W, F);
-    P.ops.push_back(op);
-    return op.out;
+    return b.conv(name + " + LeakyReLU", {b.seg(src, name, "", F, 3, 1)}, F, 2);
   };
   auto up = [&](const std::string& name, int src) {
     const TensorSpec t = P.tensors[src];
-    const int out = tensor(2 * t.H, 2 * t.W, F);
+    const int out = b.tensor(2 * t.H, 2 * t.W, F);
     for (int ph = 0; ph < 4; ++ph) {
       const int pi = ph >> 1, pj = ph & 1;
       OpSpec op;
       op.kind = OP_CONV;
-      op.label = prefix + name + " phase (" + std::to_string(pi) + "," + std::to_string(pj) + ") + LeakyReLU";
-      SegSpec sg{src, prefix + name, "", 0, F, 1 + pi, 1 + pj, 1, 0};
+      op.label = name + " phase (" + std::to_string(pi) + "," + std::to_string(pj) + ") + LeakyReLU";
+      SegSpec sg = b.seg(src, name, "", 0, F, 1, 1, 0);
+      sg.kh = 1 + pi;
+      sg.kw = 1 + pj;
       sg.convt_phase = ph;
       op.segs = {sg};
       op.N = F;
@@ -72,7 +54,7 @@ IoSpec append_protonet(Plan& P, const std::string& prefix, int x, int F, int k, 
       op.cov_x1 = 2 * t.W;
       op.flops = 2.0 * t.H * t.W * F * (double)((1 + pi) * (1 + pj)) * F;
       op.out = out;
-      P.ops.push_back(op);
+      b.emit(op);
     }
     return out;
   };
@@ -81,55 +63,30 @@ IoSpec append_protonet(Plan& P, const std::string& prefix, int x, int F, int k, 
   x = conv3("_layers_2.0.0", x);
   x = up("_upsample_layer_2", x);
   x = conv3("_layers_3.0.0", x);
-  const TensorSpec t = P.tensors[x];
-  OpSpec o;
-  o.kind = OP_CONV;
-  o.label = prefix + "_output_layer + LeakyReLU -> fp32 NHWC";
-  o.segs = {SegSpec{x, "", "", 0, F, 1, 1, 1, 0}};
-  // as a one-head "block-diagonal" 1x1 so the engine can fuse it into the 3x3 conv's epilogue
-  // (conv3x3 EPI 1: MFMA on the rounded 3x3 output, fp32 partial sums of the 128-channel tiles
-  // added into the output, LeakyReLU applied by a pass over the k output channels afterwards)
-  o.stack_w = {prefix + "_output_layer"};
-  o.stack_n = {k};
-  o.diag_in_off = {0};
-  o.diag_out_off = {0};
-  const IoSpec spec{t.H, t.W, k, (k + 3) / 4 * 4};
-  o.N = spec.cpad;
-  o.act = 2;
-  o.flops = 2.0 * t.H * t.W * k * (double)F;
-  o.out = -1 - out_slot;
-  P.ops.push_back(o);
-  return spec;
+  // the output layer as a one-head "block-diagonal" 1x1 so the engine can fuse it into the 3x3
+  // conv's epilogue (conv3x3 EPI 1: MFMA on the rounded 3x3 output, fp32 partial sums of the
+  // 128-channel tiles added into the output, LeakyReLU applied by a pass over the k output channels
+  // afterwards)
+  return b.block_diag_1x1("_output_layer + LeakyReLU -> fp32 NHWC", x, {"_output_layer"}, {k}, F, 2, out_slot);
 }
 
 int build_plan_protonet(const tv_model_desc& d, Plan* plan) {
   const int F = d.channels[0], k = d.head_channels[0];
-  const int vec = 16 / dtype_size(d.compute_dtype);
-  if (d.n_heads != 1 || F < 1 || F % vec || k < 1 || d.in_h < 1 || d.in_w < 1 || d.compute_dtype < 0 ||
-      d.compute_dtype > 2) {
+  const bool dtype_ok = d.compute_dtype >= 0 && d.compute_dtype <= 2;
+  const int vec = dtype_ok ? 16 / dtype_size(d.compute_dtype) : 8;  // (8: what an unknown dtype's refusal has always named)
+  if (!dtype_ok || d.n_heads != 1 || F < 1 || F % vec || k < 1 || d.in_h < 1 || d.in_w < 1) {
     set_error("protonet desc: need channels[0] = feature_depth (multiple of " + std::to_string(vec) +
               "), one head of n_prototype_masks channels, in_h/in_w = fpn[0] size");
     return TV_EINVAL;
   }
   *plan = Plan();
-  Plan& P = *plan;
-  P.in_channels = F;
-  P.tensors.push_back({d.in_h, d.in_w, F});
-  {
-    OpSpec op;
-    op.kind = OP_LAYOUT_IN;
-    op.label = "fpn[0] NCHW fp32 -> NHWC";
-    op.out = 0;
-    op.N = F;
-    P.ops.push_back(op);
-  }
-  const IoSpec o = append_protonet(P, "", 0, F, k, 0);
-  for (const ParamInfo& p : P.params) P.names.insert(p.name);
-  P.out_c = o.C;
-  P.out_cpad = o.cpad;
-  P.out_h = o.H;
-  P.out_w = o.W;
-  for (auto& op : P.ops) P.flops_per_frame += op.flops;
+  PlanBuilder b{*plan};
+  plan->in_channels = F;
+  OpSpec op;
+  op.kind = OP_LAYOUT_IN;
+  op.label = "fpn[0] NCHW fp32 -> NHWC";
+  op.N = F;
+  b.single_output(append_protonet(*plan, "", b.emit(op, d.in_h, d.in_w, F), F, k, 0));
   return TV_OK;
 }
 

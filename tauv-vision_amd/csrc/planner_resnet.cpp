@@ -16,39 +16,26 @@
 //        * the tapped blocks layer2.1 and layer3.1: conv2 stores bn2(conv2(h)) with no activation —
 //          the tap, which is the output of bn2, before the add and the ReLU — and OP_ADD_RELU forms
 //          relu(tap + x) for the next layer; layer4.1 ends at its tap (its add and ReLU feed nothing)
-#include "common.h"
-#include "planner.h"
+#include "plan_builder.h"
 
 namespace tv {
 namespace {
 
-struct ResnetWalker {
-  Plan& P;
-  const std::string pre;
-
-  void add(const std::string& n, std::vector<int64_t> s) { P.params.push_back({pre + n, std::move(s)}); }
-  void conv_p(const std::string& p, int cout, int cin, int k) { add(p + ".weight", {cout, cin, k, k}); }
-  void bn_p(const std::string& p, int c) {
-    add(p + ".weight", {c});
-    add(p + ".bias", {c});
-    add(p + ".running_mean", {c});
-    add(p + ".running_var", {c});
-    add(p + ".num_batches_tracked", {});
-  }
-  void params() {
-    conv_p("conv1", 64, 3, 7);
+struct ResnetWalker : PlanBuilder {  // `prefix` in front of every key and label
+  void params() {  // every conv bias-free
+    conv_p("conv1", 64, 3, 7, false);
     bn_p("bn1", 64);
     int cin = 64;
     for (int L = 1; L <= 4; ++L) {
       const int c = 64 << (L - 1);
       for (int b = 0; b < 2; ++b) {
         const std::string p = "layer" + std::to_string(L) + "." + std::to_string(b);
-        conv_p(p + ".conv1", c, b ? c : cin, 3);
+        conv_p(p + ".conv1", c, b ? c : cin, 3, false);
         bn_p(p + ".bn1", c);
-        conv_p(p + ".conv2", c, c, 3);
+        conv_p(p + ".conv2", c, c, 3, false);
         bn_p(p + ".bn2", c);
         if (!b && L > 1) {
-          conv_p(p + ".downsample.0", c, cin, 1);
+          conv_p(p + ".downsample.0", c, cin, 1, false);
           bn_p(p + ".downsample.1", c);
         }
       }
@@ -56,51 +43,21 @@ struct ResnetWalker {
     }
   }
 
-  int tensor(int H, int W, int C) {
-    P.tensors.push_back({H, W, C});
-    return (int)P.tensors.size() - 1;
-  }
-  static int half(int x) { return (x - 1) / 2 + 1; }  // k = 2 pad + 1, stride 2: (x + 2 pad - k) / 2 + 1
-
-  int conv(const std::string& label, std::vector<SegSpec> segs, int Ho, int Wo, int N, int act) {
-    OpSpec op;
-    op.kind = OP_CONV;
-    op.label = pre + label;
-    op.N = N;
-    op.act = act;
-    for (const SegSpec& sg : segs)
-      op.flops += 2.0 * Ho * Wo * N * (double)(sg.kh * (sg.row_expand ? sg.row_expand : sg.kw) * sg.cin);
-    op.segs = std::move(segs);
-    op.out = tensor(Ho, Wo, N);
-    P.ops.push_back(op);
-    return op.out;
-  }
-  SegSpec seg(int src, const std::string& p, const std::string& bn, int cin, int k, int stride) {
-    return SegSpec{src, pre + p, pre + bn, 0, cin, k, k, stride, k / 2};
-  }
-  int elementwise(int kind, const std::string& label, int src, int add, int H, int W, int C) {
+  // an elementwise (stride 1) or 3x3 / padding 1 window (stride 2, floor mode) op over `src`
+  int elementwise(int kind, const std::string& label, int src, int add, int stride) {
+    const TensorSpec t = P.tensors[src];
     OpSpec op;
     op.kind = kind;
-    op.label = pre + label;
+    op.label = label;
     op.src = src;
     op.add = add;
-    op.N = C;
-    op.act = 0;
-    op.out = tensor(H, W, C);
-    P.ops.push_back(op);
-    return op.out;
+    op.N = t.C;
+    return emit(op, out_dim(t.H, 3, stride, 1), out_dim(t.W, 3, stride, 1), t.C);
   }
 
   std::vector<int> forward(int img) {
-    const TensorSpec im = P.tensors[img];
-    SegSpec stem = seg(img, "conv1", "bn1", 3, 7, 2);
-    stem.kw = 1;
-    stem.pad_w = 0;
-    stem.row_expand = 7;
-    int H = half(im.H), W = half(im.W);
-    int x = conv("conv1 + bn1 + ReLU", {stem}, H, W, 64, 1);
-    H = half(H), W = half(W);
-    x = elementwise(OP_MAXPOOL3S2, "maxpool", x, -1, H, W, 64);
+    int x = conv("conv1 + bn1 + ReLU", {stem7(img, "conv1", "bn1", 2)}, 64, 1);
+    x = elementwise(OP_MAXPOOL3S2, "maxpool", x, -1, 2);
     std::vector<int> taps;
     int cin = 64;
     for (int L = 1; L <= 4; ++L) {
@@ -108,20 +65,17 @@ struct ResnetWalker {
       for (int b = 0; b < 2; ++b) {
         const std::string p = "layer" + std::to_string(L) + "." + std::to_string(b);
         const int stride = !b && L > 1 ? 2 : 1;
-        if (stride == 2) H = half(H), W = half(W);
-        const int h = conv(p + ".conv1 + bn1 + ReLU", {seg(x, p + ".conv1", p + ".bn1", b ? c : cin, 3, stride)}, H, W, c, 1);
+        const int h = conv(p + ".conv1 + bn1 + ReLU", {seg(x, p + ".conv1", p + ".bn1", b ? c : cin, 3, stride)}, c, 1);
         const SegSpec c2 = seg(h, p + ".conv2", p + ".bn2", c, 3, 1);
         if (b && L > 1) {  // a tapped block
-          const int tap = conv(p + ".conv2 + bn2 (tap)", {c2}, H, W, c, 0);
+          const int tap = conv(p + ".conv2 + bn2 (tap)", {c2}, c, 0);
           taps.push_back(tap);
-          if (L < 4) x = elementwise(OP_ADD_RELU, p + " relu(bn2 + x)", tap, x, H, W, c);
+          if (L < 4) x = elementwise(OP_ADD_RELU, p + " relu(bn2 + x)", tap, x, 1);
         } else if (stride == 2) {
-          SegSpec ds = seg(x, p + ".downsample.0", p + ".downsample.1", cin, 1, 2);
-          x = conv(p + ".conv2 + bn2 + downsample + ReLU", {c2, ds}, H, W, c, 1);
+          x = conv(p + ".conv2 + bn2 + downsample + ReLU", {c2, seg(x, p + ".downsample.0", p + ".downsample.1", cin, 1, 2)},
+                   c, 1);
         } else {
-          SegSpec id{x, "", "", 0, c, 1, 1, 1, 0};
-          id.identity = true;
-          x = conv(p + ".conv2 + bn2 + x + ReLU", {c2, id}, H, W, c, 1);
+          x = conv(p + ".conv2 + bn2 + x + ReLU", {c2, identity(x, c)}, c, 1);
         }
       }
       cin = c;
@@ -133,7 +87,7 @@ struct ResnetWalker {
 }  // namespace
 
 std::vector<int> append_resnet18(Plan& P, const std::string& prefix, int img) {
-  ResnetWalker w{P, prefix};
+  ResnetWalker w{{P, prefix}};
   w.params();
   return w.forward(img);
 }
@@ -161,21 +115,11 @@ int build_plan_resnet(const tv_model_desc& d, Plan* plan) {
   }
   *plan = Plan();
   Plan& P = *plan;
-  // the image staged row-expanded for the 7x7 stem, as build_plan's (planner.cpp)
-  const int vec = 16 / dtype_size(d.compute_dtype);
-  P.in_cpad = (7 * 3 + vec - 1) / vec * vec;
+  PlanBuilder b{P};
+  const int img = b.staged_image(d, "input staging (NCHW fp32 -> NHWC)");
   P.in_channels = 3;
-  P.tensors.push_back({d.in_h, d.in_w, P.in_cpad});
-  {
-    OpSpec op;
-    op.kind = OP_PREP;
-    op.label = "input staging (NCHW fp32 -> NHWC)";
-    op.out = 0;
-    op.N = P.in_cpad;
-    P.ops.push_back(op);
-  }
   P.ins.push_back(IoSpec{d.in_h, d.in_w, 3, 3});
-  const std::vector<int> taps = append_resnet18(P, d.arch == TV_ARCH_YOLACT ? "_backbone._feature_extractor." : "", 0);
+  const std::vector<int> taps = append_resnet18(P, d.arch == TV_ARCH_YOLACT ? "_backbone._feature_extractor." : "", img);
   if (d.arch == TV_ARCH_YOLACT) {
     append_yolact_head(P, hd, taps);
   } else {
@@ -186,14 +130,11 @@ int build_plan_resnet(const tv_model_desc& d, Plan* plan) {
       o.label = "layer" + std::to_string(i + 2) + ".1.bn2 -> fp32 NHWC";
       o.src = taps[i];
       o.N = t.C;
-      o.act = 0;
       o.out = -1 - (int)i;
       P.outs.push_back(IoSpec{t.H, t.W, t.C, t.C});
-      P.ops.push_back(o);
+      b.emit(o);
     }
   }
-  for (const ParamInfo& p : P.params) P.names.insert(p.name);
-  for (auto& op : P.ops) P.flops_per_frame += op.flops;
   return TV_OK;
 }
 

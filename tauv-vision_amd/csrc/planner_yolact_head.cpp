@@ -24,31 +24,17 @@
 // Two reference quirks are kept: one PredictionHead for all levels (each level's ops read the same
 // weights), and the pixel-major, aspect-ratio-inner row order of permute(0, 2, 3, 1).reshape
 // (prediction_head.py:112-113), which differs from get_anchor's ratio-major blocks (anchors.py).
-#include "common.h"
-#include "planner.h"
+#include "plan_builder.h"
 
 namespace tv {
 namespace {
 
-struct HeadWalker {
+struct HeadWalker : PlanBuilder {
   const tv_model_desc& d;
-  Plan& P;
   const int F;
   const bool head;
   const std::vector<int>& given;  // the backbone maps when they are tensors of the plan already (else empty)
 
-  void add(const std::string& n, std::vector<int64_t> s) { P.params.push_back({n, std::move(s)}); }
-  void conv_p(const std::string& p, int cout, int cin, int k, bool bias = true) {
-    add(p + ".weight", {cout, cin, k, k});
-    if (bias) add(p + ".bias", {cout});
-  }
-  void bn_p(const std::string& p, int c) {
-    add(p + ".weight", {c});
-    add(p + ".bias", {c});
-    add(p + ".running_mean", {c});
-    add(p + ".running_var", {c});
-    add(p + ".num_batches_tracked", {});
-  }
   void fpn_params(const std::string& p) {
     for (int i = 0; i < d.n_levels; ++i) conv_p(p + "_lateral_layers." + std::to_string(i), F, d.channels[1 + i], 1);
     for (int i = 0; i < d.downsamples; ++i) conv_p(p + "_downsample_layers." + std::to_string(i), F, F, 3);
@@ -68,50 +54,16 @@ struct HeadWalker {
     for (int i = 0; i < n; ++i) bn_p(p + g + "_bn_layers." + std::to_string(i), F);
   }
 
-  int tensor(int H, int W, int C, bool f32 = false) {
-    TensorSpec t{H, W, C};
-    t.f32 = f32;
-    P.tensors.push_back(t);
-    return (int)P.tensors.size() - 1;
-  }
-  int conv(const std::string& label, std::vector<SegSpec> segs, int N, int act) {
-    const TensorSpec s0 = P.tensors[segs[0].src];
-    const int Ho = (s0.H + 2 * segs[0].pad - segs[0].kh) / segs[0].stride + 1;
-    const int Wo = (s0.W + 2 * segs[0].pad - segs[0].kw) / segs[0].stride + 1;
-    OpSpec op;
-    op.kind = OP_CONV;
-    op.label = label;
-    op.N = N;
-    op.act = act;
-    for (const SegSpec& sg : segs) op.flops += 2.0 * Ho * Wo * N * (double)(sg.kh * sg.kw * sg.cin);
-    op.segs = std::move(segs);
-    op.out = tensor(Ho, Wo, N);
-    P.ops.push_back(op);
-    return op.out;
-  }
-  static SegSpec seg(int src, const std::string& w, const std::string& bn, int cin, int k, int stride) {
-    return SegSpec{src, w, bn, 0, cin, k, k, stride, k / 2};
-  }
-  // `src` added as it is (bn empty) or through an eval BatchNorm (scaled per channel, shift in the bias)
-  static SegSpec identity(int src, int c, const std::string& bn) {
-    SegSpec sg{src, "", bn, 0, c, 1, 1, 1, 0};
-    sg.identity = true;
-    return sg;
-  }
-
   // backbone map i, one of the caller's inputs, as an NHWC tensor
   int layout_in(int i) {
     const int c = d.channels[1 + i];
-    const int x = tensor(d.map_h[i], d.map_w[i], c);
     P.ins.push_back(IoSpec{d.map_h[i], d.map_w[i], c, c});
     OpSpec op;
     op.kind = OP_LAYOUT_IN;
     op.label = "backbone map " + std::to_string(i) + " NCHW fp32 -> NHWC";
-    op.out = x;
     op.N = c;
     op.io = i;
-    P.ops.push_back(op);
-    return x;
+    return emit(op, d.map_h[i], d.map_w[i], c);
   }
 
   // feature_pyramid.py:44-58 -> the FPN levels' tensors
@@ -132,8 +84,7 @@ struct HeadWalker {
       op.add = lat[i];
       op.out = lat[i];
       op.N = F;
-      op.act = 0;
-      P.ops.push_back(op);
+      emit(op);
     }
     std::vector<int> lv;
     for (int i = 0; i < n; ++i) {
@@ -164,22 +115,9 @@ struct HeadWalker {
 
   // a final 3x3 conv (or the three stacked along N) into an fp32 raw tensor
   int final_conv(const std::string& label, int x, const std::vector<std::string>& names, const std::vector<int>& ns) {
-    const TensorSpec t = P.tensors[x];
     int n = 0;
     for (int v : ns) n += v;
-    OpSpec op;
-    op.kind = OP_CONV;
-    op.label = label;
-    op.segs = {SegSpec{x, "", "", 0, F, 3, 3, 1, 1}};
-    op.stack_w = names;
-    op.stack_n = ns;
-    op.N = (n + 3) / 4 * 4;  // the fp32 store writes whole 16-byte vectors: zero weight rows up to it
-    op.act = 0;
-    op.out_f32 = true;
-    op.flops = 2.0 * t.H * t.W * n * 9.0 * F;
-    op.out = tensor(t.H, t.W, op.N, true);
-    P.ops.push_back(op);
-    return op.out;
+    return stacked_conv3x3(label, x, names, ns, pad4(n), 0, true);
   }
 
   void run() {
@@ -187,18 +125,8 @@ struct HeadWalker {
     fpn_params(fp);
     const std::vector<int> lv = fpn(fp);
     if (!head) {
-      for (size_t l = 0; l < lv.size(); ++l) {  // each level into the caller's fp32 NHWC buffer: an identity 1x1 GEMM
-        const TensorSpec t = P.tensors[lv[l]];
-        OpSpec o;
-        o.kind = OP_CONV;
-        o.label = "fpn[" + std::to_string(l) + "] -> fp32 NHWC";
-        o.segs = {identity(lv[l], F, "")};
-        o.N = F;
-        o.act = 0;
-        o.out = -1 - (int)l;
-        P.outs.push_back(IoSpec{t.H, t.W, F, F});
-        P.ops.push_back(o);
-      }
+      for (size_t l = 0; l < lv.size(); ++l)  // each level into the caller's fp32 NHWC buffer
+        P.outs.push_back(to_caller_f32(lv[l], (int)l, "fpn[" + std::to_string(l) + "] -> fp32 NHWC"));
       return;
     }
     const int k = d.head_channels[0], C1 = d.head_channels[1] + 1, nar = d.n_aspect_ratios;
@@ -223,9 +151,6 @@ struct HeadWalker {
       OpSpec sc;
       sc.kind = OP_HEAD_SCATTER;
       sc.label = lp + "raw heads -> classification / box_encoding / tanh(mask_coeff)";
-      sc.out = -1;
-      sc.N = 0;
-      sc.act = 0;
       if (stacked) {
         const int raw = final_conv(lp + "final 3x3 convs (stacked)", x, fin, {nar * C1, nar * 4, nar * k});
         int c0 = 0;
@@ -241,7 +166,7 @@ struct HeadWalker {
           sc.parts.push_back(ScatterPart{raw, 0, nar * width[j], j, row0, width[j], j == 2});
         }
       }
-      P.ops.push_back(sc);
+      emit(sc);
       row0 += t.H * t.W * nar;
     }
   }
@@ -298,7 +223,7 @@ int check_yolact_head_desc(const tv_model_desc& d) {
 }
 
 void append_yolact_head(Plan& P, const tv_model_desc& d, const std::vector<int>& maps) {
-  HeadWalker w{d, P, d.channels[0], d.arch != TV_ARCH_YOLACT_FPN, maps};
+  HeadWalker w{{P}, d, d.channels[0], d.arch != TV_ARCH_YOLACT_FPN, maps};
   w.run();
 }
 
@@ -307,8 +232,6 @@ int build_plan_yolact_head(const tv_model_desc& d, Plan* plan) {
   if (rc) return rc;
   *plan = Plan();
   append_yolact_head(*plan, d, {});
-  for (const ParamInfo& p : plan->params) plan->names.insert(p.name);
-  for (auto& op : plan->ops) plan->flops_per_frame += op.flops;
   plan->in_channels = d.channels[1];
   return TV_OK;
 }
