@@ -433,6 +433,48 @@ int tv_match_keypoints(const float* obj_records, const int32_t* obj_counts, cons
                        int32_t n_keypoints, int32_t max_slots, int32_t B, int32_t K, int32_t K_kp, int32_t* kp_det,
                        int32_t* slot_kp, int32_t* n_matched, void* stream);
 
+/* The detection-to-truth matching of the reference's evaluation scripts (centernet/scripts/evaluate.py:
+ * 188-203, evaluate_keypoints.py:143-153) for B images in one launch, and the counts of their precision
+ * and recall for T score thresholds at once. Device pointers (cols is a host array), async on `stream`,
+ * no workspace, no host synchronisation (graph-capturable).
+ * records [B, K, rec_stride] fp32 with counts [B] int32 (clamped to [0, K]); cols[6]: the columns of label,
+ * score, y, x, h, w (a tv_decode record: 0, 1, 2, 3, 4, 5; a tv_yolact_detection_records row: 1, 3, 4, 5, 6,
+ * 7). Truths of image b: truth_valid [B, N] u8 (bool), truth_label [B, N] int64, truth_center [B, N, 2]
+ * fp32 (y, x), truth_size [B, N, 2] fp32 (h, w; may be NULL when mode == 1). score_thresholds [T] fp32, in
+ * any order.
+ * The records of an image are walked in descending score, the LATER record first among equal scores
+ * (reversed(sorted(.., key=score)): a stable sort, reversed); the records need not arrive sorted. Each
+ * takes the first truth, in truth order, that is valid, not yet taken, has int(label) equal to its own and
+ * passes the match test; that truth is then taken. The first qualifying truth wins, not the best one.
+ *   mode 0 (box, evaluate.py:106-130): ya = max(y1 - h1/2, y2 - h2/2), xa likewise, yb = min(y1 + h1/2,
+ *     y2 + h2/2), xb likewise, inter = abs(max(yb - ya, 0) * max(xb - xa, 0)), iou = 0 if inter == 0 else
+ *     inter / (w1 h1 + w2 h2 - inter); the pair passes when iou >= match_threshold. With match_threshold
+ *     <= 0 every pair of equal labels passes, disjoint boxes included, as in the reference.
+ *   mode 1 (centre, evaluate_keypoints.py:61-71): the pair passes unless sqrt((y1 - y2)^2 + (x1 - x2)^2) >
+ *     match_threshold. Only label, score, y, x of the records are read.
+ * Both in double on the fp32 values, uncontracted, in the order written (Python's max / min: the first
+ * argument unless the second is strictly beyond it).
+ * The detections of the reference at score threshold t are the records with score >= t (fp32 compare, an
+ * equal score counts): a prefix of the walk, so one walk serves every threshold. A NaN score passes no
+ * threshold and walks last (the reference never produces one: outside its behaviour).
+ * Outputs:
+ *   det_truth [B, K] int32   the truth index record k took, or -1; rows k >= counts[b] are -1. Every
+ *                            element is written by every call.
+ *   totals [2T + 1] int64    n_tp[T], n_detections[T], n_truth. The call ADDS to them (integer atomics):
+ *                            n_tp[t] += records with score >= t that took a truth, n_detections[t] += records
+ *                            with score >= t, n_truth += valid truths. A data set is a run of calls on one
+ *                            zeroed buffer, in any order. precision = n_tp / n_detections (1 when there is
+ *                            no detection), recall = n_tp / n_truth.
+ * One workgroup per image; the K x N match tests run in parallel into 64-bit masks in LDS, one wave walks.
+ * TV_EINVAL before any launch, with nothing written: null pointers (truth_size only when mode == 0), B < 0,
+ * K outside 0..1024, N outside 1..256, T outside 1..64, mode not 0 or 1, rec_stride < 1, a column outside
+ * [0, rec_stride). B == 0 or K == 0 succeeds and launches nothing (nothing is added). */
+int tv_evaluate_detections(const float* records, int32_t rec_stride, const int32_t* counts, const int32_t cols[6],
+                           int32_t B, int32_t K, const uint8_t* truth_valid, const int64_t* truth_label,
+                           const float* truth_center, const float* truth_size, int32_t N, int32_t mode,
+                           double match_threshold, const float* score_thresholds, int32_t T, int32_t* det_truth,
+                           int64_t* totals, void* stream);
+
 /* Training targets of the CenterNet loss (loss.py:31-135), fp32, device pointers, async on `stream`.
  * generate_heatmap (loss.py:31-72): valid [B,n_objects] u8 (bool), label [B,n_objects] int64,
  *   center [B,n_objects,2] fp32 (y, x normalised) -> heatmap [B,n_labels,in_h/ratio,in_w/ratio]:

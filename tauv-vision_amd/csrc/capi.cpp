@@ -563,6 +563,17 @@ int tv_match_keypoints(const float* obj_records, const int32_t* obj_counts, cons
                                            (hipStream_t)stream); })
 }
 
+int tv_evaluate_detections(const float* records, int32_t rec_stride, const int32_t* counts, const int32_t cols[6],
+                           int32_t B, int32_t K, const uint8_t* truth_valid, const int64_t* truth_label,
+                           const float* truth_center, const float* truth_size, int32_t N, int32_t mode,
+                           double match_threshold, const float* score_thresholds, int32_t T, int32_t* det_truth,
+                           int64_t* totals, void* stream) {
+  TV_GUARD({ return launch_evaluate_detections(records, rec_stride, counts, cols, B, K, truth_valid,
+                                               (const long long*)truth_label, truth_center, truth_size, N, mode,
+                                               match_threshold, score_thresholds, T, det_truth, (long long*)totals,
+                                               (hipStream_t)stream); })
+}
+
 int tv_decode_workspace_size(int32_t B, int32_t C, int32_t H, int32_t W, int32_t K, int64_t* bytes) {
   if (!bytes || B < 1 || C < 1 || H < 1 || W < 1 || K < 1) { set_error("bad argument"); return TV_EINVAL; }
   *bytes = (int64_t)decode_workspace_bytes(B, C, H, W, K);

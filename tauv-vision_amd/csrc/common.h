@@ -470,6 +470,13 @@ int launch_match_keypoints(const float* obj_records, const int* obj_counts, cons
                            const int* kp_counts, const int* owner_label, const int* owner_slot, int n_keypoints,
                            int max_slots, int B, int K, int K_kp, int* kp_det, int* slot_kp, int* n_matched,
                            hipStream_t s);
+// Detection-to-truth matching and the precision / recall counts of the reference's evaluate scripts
+// (evaluate.hip): the contract is tv_evaluate_detections' in include/tauv_vision_amd.h. Arguments are
+// checked here (return 1 with the error text set); B * K == 0 launches nothing.
+int launch_evaluate_detections(const float* records, int rec_stride, const int* counts, const int* cols, int B, int K,
+                               const uint8_t* truth_valid, const long long* truth_label, const float* truth_center,
+                               const float* truth_size, int N, int mode, double match_threshold,
+                               const float* score_thresholds, int T, int* det_truth, long long* totals, hipStream_t s);
 int launch_uncovered_copy(const void* add, int add_ldc, void* out, int out_ldc, int C, int B,
                           int tH, int tW, int y0, int y1, int x0, int x1, int dtype,
                           hipStream_t s);

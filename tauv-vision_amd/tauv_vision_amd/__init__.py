@@ -12,6 +12,10 @@ from .decode import (Detection, DeviceKeypointDecoder, KeypointDetection, Keypoi
 from .yolact import (FeaturePyramid, Masknet, PredictionHead, Resnet101Backbone, Yolact, YolactConfig,  # noqa: F401
                      YolactDetections, YolactDetector, YolactHead, detection_records, yolact_head_state_dict)
 from .localize import DeviceLocalizer, localize_detections, localize_masks  # noqa: F401
+# the module stays `tauv_vision_amd.evaluate` (the reference's scripts are evaluate.py / evaluate_keypoints.py)
+from .evaluate import (DeviceEvaluator, EvaluationResult, evaluate_keypoints_precision_recall,  # noqa: F401
+                       evaluate_keypoints_precision_recall_curve, evaluate_precision_recall,
+                       evaluate_precision_recall_curve)
 # the loss itself is tauv_vision_amd.loss.loss (`from tauv_vision_amd.loss import loss`, as the reference's
 # train.py imports it): the package attribute `loss` stays the module
 from .loss import (Angle, Losses, PoseSample, angle_in_range, angle_loss, angle_range, depth_loss,  # noqa: F401
