@@ -405,6 +405,45 @@ int tv_localize_masks(const float* masks, int32_t mh, int32_t mw, const int32_t*
                       int32_t dh, int32_t dw, int32_t bound_by_box, double fx, double fy, double cx, double cy,
                       double min_depth_sum, double min_z, float* out, void* stream);
 
+/* The YOLACT instance masks at the size of the camera frame: what both reference callers do with the
+ * assembled masks. evaluate_batch.py:98-102 runs F.interpolate(mask, (in_h, in_w), mode="bilinear") and
+ * mask > 0.5; yolact_node.py:135,143 runs F.interpolate(mask, (H_raw, W_raw)) (nearest), copies [n, H, W]
+ * fp32 to the host and uses mask_np > 0.5 (:184); both then blend every mask into the colour frame
+ * (utils/plot.py:148-152, restated in evaluate_batch.py:136-139). Device pointers, async on `stream`, no
+ * workspace, no host synchronisation (graph-capturable). The up-sampled fp32 mask is never stored.
+ * masks [B, n, mh, mw] fp32 contiguous and counts [B] as tv_yolact_assemble_masks_indexed /
+ * tv_yolact_fast_nms_batched write them; (H, W) the frame size; mode TV_FRAME_BILINEAR or
+ * TV_FRAME_NEAREST. A frame pixel (y, x) of detection d < counts[b] is selected when its up-sampled
+ * value is > 0.5 (strict; a NaN is not). Nearest: masks[b, d, sy(y), sx(x)] with tv_localize_masks' map
+ * sx(x) = min((int)floorf((float)x * ((float)mw / (float)W)), mw - 1), likewise sy. Bilinear: torch's
+ * align_corners=False arithmetic in fp32 per axis — scale = (float)in / (float)out, src = max(fma(scale,
+ * dst + 0.5, -0.5), 0), i0 = (int)src, i1 = min(i0 + 1, in - 1), weights l1 = src - i0 and l0 = 1 - l1 —
+ * and the value fma(t0, h0, t1 * h1) of the row blends t = fma(left, w0, right * w1) (tv_preprocess_u8's
+ * arithmetic).
+ * Every element of every output is written by every call:
+ *   bits [B, n, H, ceil(W / 32)] uint32: pixel x is bit x % 32 of word x / 32; bits at x >= W are 0; rows
+ *     d >= counts[b] are all zero.
+ *   area [B, n] int32: the number of set bits of each row (0 past the count).
+ *   overlay [B, H, W, 3] uint8, with frames [B, H, W, 3] uint8 (both NULL or both given; they may be the
+ *     same buffer): a pixel starts from the frame's value and, for d = 0 .. counts[b] - 1 in that order,
+ *     where its bit is set, each channel becomes (pix + colour[c]) >> 1 — exactly numpy's
+ *     uint8(0.5 colour + 0.5 pix), which truncates. colour = palette[min(class_id, n_colours - 1)] (what
+ *     ListedColormap returns for an index past its end; a negative id takes row 0), class_id = column 1 of
+ *     records [B, n, 8] (tv_yolact_detection_records), palette [n_colours, 3] uint8 on the device.
+ * bound_by_box != 0 (with det [B, n] int64, box [B, A, 4] as for tv_localize_masks, for masks assembled
+ * with that box, which are zero outside it): a wave of 64 frame columns skips a detection whose box crop
+ * — widened by one prototype pixel for bilinear, whose value above 0.5 needs a non-zero tap — cannot reach
+ * its row and columns. Bit-equal to bound_by_box == 0. A det entry outside [0, A) is not bounded.
+ * TV_EINVAL before any launch: null masks, counts, bits or area; non-positive mh, mw, H, W; an unknown
+ * mode; bound_by_box without det, box or A >= 1; frames without overlay, records or palette (or overlay
+ * without frames); n_colours < 1 with frames. B * n == 0 succeeds and launches nothing. */
+#define TV_FRAME_BILINEAR 0
+#define TV_FRAME_NEAREST 1
+int tv_yolact_frame_masks(const float* masks, int32_t mh, int32_t mw, const int32_t* counts, int32_t B, int32_t n,
+                          int32_t H, int32_t W, int32_t mode, int32_t bound_by_box, const int64_t* det, const float* box,
+                          int32_t A, const uint8_t* frames, const float* records, const uint8_t* palette,
+                          int32_t n_colours, uint32_t* bits, int32_t* area, uint8_t* overlay, void* stream);
+
 /* The greedy keypoint-to-object matching of decode_keypoints() (decode.py:100-135) for B images in
  * one launch, on what tv_decode (mode 1) writes. Device pointers, async on `stream`, no workspace,
  * no host synchronisation (graph-capturable).

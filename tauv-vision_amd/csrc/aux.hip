@@ -5,6 +5,7 @@
 //  * the pad_to_match margin: target pixels that the shifted upsample does not cover get the
 //    skip tensor alone (dla.py:205-207 zero padding).
 #include "common.h"
+#include "resample_dev.h"
 
 #include <algorithm>
 
@@ -79,14 +80,7 @@ __global__ void prep_u8(const uint8_t* __restrict__ fr, int B, int H, int W, int
 // fma(scale, dst + 0.5, -0.5) clamped at 0, weights l1 = src - floor, l0 = 1 - l1, the row blend
 // fma(top, wh0, bottom * wh1) of the column blends fma(left, ww0, right * ww1)), then Normalize
 // ((v - mean) / std). One thread per output pixel; fp32 NCHW out (the Centernet.forward input).
-__device__ __forceinline__ void lin_index(int d, int in, float scale, int& i0, int& i1, float& l0, float& l1) {
-  float src = __fmaf_rn(scale, (float)d + 0.5f, -0.5f);
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  l1 = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
-  l0 = 1.f - l1;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-}
+using resample::lin_index;  // (resample_dev.h: shared with bilinear_add and frame_masks)
 
 __global__ void preprocess_u8(const uint8_t* __restrict__ fr, int B, int Hs, int Ws, int Ho, int Wo, float sh, float sw,
                               float* __restrict__ out) {

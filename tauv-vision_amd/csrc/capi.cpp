@@ -554,6 +554,15 @@ int tv_localize_masks(const float* masks, int32_t mh, int32_t mw, const int32_t*
                                           (hipStream_t)stream); })
 }
 
+int tv_yolact_frame_masks(const float* masks, int32_t mh, int32_t mw, const int32_t* counts, int32_t B, int32_t n,
+                          int32_t H, int32_t W, int32_t mode, int32_t bound_by_box, const int64_t* det, const float* box,
+                          int32_t A, const uint8_t* frames, const float* records, const uint8_t* palette,
+                          int32_t n_colours, uint32_t* bits, int32_t* area, uint8_t* overlay, void* stream) {
+  TV_GUARD({ return launch_yolact_frame_masks(masks, mh, mw, counts, B, n, H, W, mode, bound_by_box,
+                                              (const long long*)det, box, A, frames, records, palette, n_colours, bits,
+                                              area, overlay, (hipStream_t)stream); })
+}
+
 int tv_match_keypoints(const float* obj_records, const int32_t* obj_counts, const float* kp_records,
                        const int32_t* kp_counts, const int32_t* owner_label, const int32_t* owner_slot,
                        int32_t n_keypoints, int32_t max_slots, int32_t B, int32_t K, int32_t K_kp, int32_t* kp_det,

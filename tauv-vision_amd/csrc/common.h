@@ -463,6 +463,15 @@ int launch_localize_masks(const float* masks, int mh, int mw, const int* counts,
                           int A, int B, int n, const uint16_t* depth, int depth_batch, int dh, int dw, int bound_by_box,
                           double fx, double fy, double cx, double cy, double min_depth_sum, double min_z, float* out,
                           hipStream_t s);
+// YOLACT instance masks at frame size (yolact_frame.hip): masks [B][n][mh][mw] resized to H x W
+// (mode 0 bilinear, 1 nearest), `> 0.5`, packed to bits [B][n][H][ceil(W / 32)] with their set-bit
+// counts area [B][n] and, with frames, blended into overlay [B][H][W][3]: the contract is
+// tv_yolact_frame_masks' in include/tauv_vision_amd.h. Arguments are checked here (return 1 with the
+// error text set); B * n == 0 launches nothing.
+int launch_yolact_frame_masks(const float* masks, int mh, int mw, const int* counts, int B, int n, int H, int W, int mode,
+                              int bound_by_box, const long long* det, const float* box, int A, const uint8_t* frames,
+                              const float* records, const uint8_t* palette, int n_colours, uint32_t* bits, int* area,
+                              uint8_t* overlay, hipStream_t s);
 // Keypoint-to-object matching of decode_keypoints (keypoints.hip) on tv_decode's mode-1 records: the
 // contract is tv_match_keypoints' in include/tauv_vision_amd.h. Arguments are checked here (return 1
 // with the error text set); B == 0 launches nothing.

@@ -12,6 +12,7 @@
 // epilogue and writes the detection's 8 floats. No atomics, no workspace, no host synchronisation;
 // every output row is written by every launch.
 #include "common.h"
+#include "resample_dev.h"
 
 #include <cmath>
 
@@ -82,24 +83,6 @@ __device__ inline Region box_region(const Params& p, const float* r) {
   return g;
 }
 
-// The depth rows or columns whose nearest source pixel can lie inside [lo, hi] of an n-pixel mask
-// axis (lo, hi: the box crop's bounds at mask resolution, as assemble_mask forms them). The range
-// is widened on purpose — one source pixel for the rounding of the bounds, then two depth pixels
-// (and dn / 2^18 for fp32 index arithmetic on very large images) for the rounding of the nearest
-// map — because the mask is zero outside the crop: scanning more never changes the result.
-__device__ inline void crop_range(float lo, float hi, int n, int dn, int& d0, int& d1) {
-  d0 = 0;
-  d1 = dn - 1;
-  if (!isfinite(lo) || !isfinite(hi)) return;
-  const double l = fmin(fmax((double)lo, -1.0), (double)n), r = fmin(fmax((double)hi, -1.0), (double)n);
-  const int sl = (int)floor(l) - 1, sr = (int)ceil(r) + 1;
-  const int margin = 2 + (dn >> 18);
-  const double f = (double)dn / (double)n;
-  const double a = floor((double)sl * f) - margin, b = ceil((double)(sr + 1) * f) + margin;
-  d0 = (int)fmin(fmax(a, 0.0), (double)dn);       // dn: empty
-  d1 = (int)fmin(fmax(b, -1.0), (double)(dn - 1));
-}
-
 __device__ inline Region mask_region(const Params& p, const float* q) {
 #pragma clang fp contract(off)
   Region g;
@@ -109,16 +92,13 @@ __device__ inline Region mask_region(const Params& p, const float* q) {
   g.x1 = p.dw - 1;
   g.y1 = p.dh - 1;
   if (p.bound_by_box) {
-    // box_to_mask (boxes.py:88-103) at mask resolution, the fp32 bounds of assemble_mask
-    const float by = q[0] * (float)p.mh, bx = q[1] * (float)p.mw, bh = q[2] * (float)p.mh, bw = q[3] * (float)p.mw;
-    crop_range(bx - bw / 2, bx + bw / 2, p.mw, p.dw, g.x0, g.x1);
-    crop_range(by - bh / 2, by + bh / 2, p.mh, p.dh, g.y0, g.y1);
+    // the rows and columns that can map into the box crop (resample_dev.h)
+    resample::box_crop(q, p.mh, p.mw, p.dh, p.dw, 0.f, g.x0, g.x1, g.y0, g.y1);
   }
   return g;
 }
 
-// torch's CPU nearest F.interpolate: src = min((int)floorf(dst * scale), n - 1), scale = (float)n / (float)dn
-__device__ inline int nearest_src(int dst, float scale, int n) { return min((int)floorf((float)dst * scale), n - 1); }
+using resample::nearest_src;  // torch's CPU nearest F.interpolate map (resample_dev.h)
 
 template <bool MASK>
 __device__ inline void take(unsigned v, int xx, const float* mrow, float scale_w, int mw, unsigned& s, unsigned& c) {

@@ -6,6 +6,7 @@
 //    GEMMs' fp32 store wrote them) into the caller's three anchor-indexed outputs
 //    (prediction_head.py:111-141 + the torch.cat of model.py:55-57), tanh on the mask coefficients.
 #include "common.h"
+#include "resample_dev.h"
 
 #include <type_traits>
 
@@ -15,17 +16,7 @@
 namespace tv {
 namespace yh {
 
-// torch's upsample_bilinear2d source index and weights, align_corners=False, scale = in / out in
-// fp32 (area_pixel_compute_source_index): src = max(0, scale (d + 0.5) - 0.5), i0 = floor, the
-// second tap clamped to in - 1, l1 = src - i0, l0 = 1 - l1
-__device__ __forceinline__ void lin_index(int d, int in, float scale, int& i0, int& i1, float& l0, float& l1) {
-  float src = __fmaf_rn(scale, (float)d + 0.5f, -0.5f);
-  src = src < 0.f ? 0.f : src;
-  i0 = min((int)src, in - 1);
-  l1 = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
-  l0 = 1.f - l1;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-}
+using resample::lin_index;  // torch's upsample_bilinear2d source index and weights (resample_dev.h)
 
 template <typename T>
 struct Vec16 {

@@ -9,8 +9,9 @@ from .dla import DLABackbone  # noqa: F401
 from .decode import (Detection, DeviceKeypointDecoder, KeypointDetection, KeypointRecords, angle_decode,  # noqa: F401
                      angle_get_bins, decode, decode_keypoints, decode_keypoints_records, decode_records, depth_decode,
                      heatmap_detect, heatmap_nms, keypoint_detections_from_records)
-from .yolact import (FeaturePyramid, Masknet, PredictionHead, Resnet101Backbone, Yolact, YolactConfig,  # noqa: F401
-                     YolactDetections, YolactDetector, YolactHead, detection_records, yolact_head_state_dict)
+from .yolact import (DeviceFrameMasks, FeaturePyramid, FrameMasks, Masknet, PredictionHead,  # noqa: F401
+                     Resnet101Backbone, TAB10, Yolact, YolactConfig, YolactDetections, YolactDetector, YolactHead,
+                     detection_records, frame_masks, pack_frame_masks, unpack_frame_masks, yolact_head_state_dict)
 from .localize import DeviceLocalizer, localize_detections, localize_masks  # noqa: F401
 # the module stays `tauv_vision_amd.evaluate` (the reference's scripts are evaluate.py / evaluate_keypoints.py)
 from .evaluate import (DeviceEvaluator, EvaluationResult, evaluate_keypoints_precision_recall,  # noqa: F401

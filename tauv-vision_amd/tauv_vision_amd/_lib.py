@@ -136,6 +136,8 @@ EXPORTS = {
                            c_f64, c_f64, c_f64, c_vp, c_vp], c_i32),
     "tv_localize_masks": ([c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32,
                            c_i32, c_f64, c_f64, c_f64, c_f64, c_f64, c_f64, c_vp, c_vp], c_i32),
+    "tv_yolact_frame_masks": ([c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32,
+                               c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp], c_i32),
     "tv_match_keypoints": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
                             c_vp], c_i32),
     "tv_evaluate_detections": ([c_vp, c_i32, c_vp, ctypes.POINTER(c_i32), c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,

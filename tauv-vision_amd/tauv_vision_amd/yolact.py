@@ -346,6 +346,203 @@ def detection_records(classification: torch.Tensor, box: torch.Tensor, det: torc
     return out, confidence_out
 
 
+# ---- the instance masks at frame size (csrc/yolact_frame.hip; the contract is tv_yolact_frame_masks') ----
+
+# matplotlib's tab10 as the reference's callers turn it into a colour (evaluate_batch.py:109-111,
+# utils/plot.py:121-123): row i is int(255 * (v / 255)) of the i-th tab10 entry v
+TAB10 = torch.tensor([[31, 119, 180], [255, 127, 14], [44, 160, 44], [214, 39, 40], [148, 103, 189], [140, 86, 75],
+                      [227, 119, 194], [127, 127, 127], [188, 189, 34], [23, 190, 207]], dtype=torch.uint8)
+FRAME_MODES = {"bilinear": 0, "nearest": 1}  # TV_FRAME_*
+
+
+class FrameMasks(NamedTuple):
+    """bits [B, n, H, ceil(W / 32)] uint32 (pixel x is bit x % 32 of word x // 32; zero at x >= W and in
+    rows at or past counts[b]), area [B, n] int32 (set bits per row), overlay [B, H, W, 3] uint8 or None
+    without frames."""
+    bits: torch.Tensor
+    area: torch.Tensor
+    overlay: Optional[torch.Tensor]
+
+
+def _frame_mode(mode):
+    if mode not in FRAME_MODES:
+        raise ValueError(f"frame_masks: mode must be one of {sorted(FRAME_MODES)}, got {mode!r}")
+    return FRAME_MODES[mode]
+
+
+def _frame_out(t, shape, dtype, device, name):
+    """A caller-owned output of frame_masks (or a fresh one): contiguous, of exactly `shape`."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device \
+            or not t.is_contiguous():
+        raise ValueError(f"frame_masks: out.{name} must be a contiguous {dtype} {list(shape)} tensor on {device}")
+    return t
+
+
+def frame_masks(masks: torch.Tensor, counts: torch.Tensor, size, mode: str = "bilinear",
+                det: Optional[torch.Tensor] = None, box: Optional[torch.Tensor] = None,
+                frames: Optional[torch.Tensor] = None, records: Optional[torch.Tensor] = None,
+                palette: Optional[torch.Tensor] = None, out: Optional[FrameMasks] = None) -> FrameMasks:
+    """The instance masks at frame size for B images in one step: masks [B, n, mh, mw] fp32
+    (assemble_masks_indexed output) and counts [B] int32 -> F.interpolate(mask, size, mode) > 0.5
+    (evaluate_batch.py:98-102 with "bilinear", yolact_node.py:135,143,184 with "nearest") as packed bits
+    and their areas; the up-sampled fp32 mask is never stored. size = (H, W) of the frame.
+
+    det [B, n] int64 with box [B, A, 4] (BatchedNMS / box_decode outputs; both or neither): for masks
+    that were assembled with `box`, which are zero outside it, only the box crop is evaluated — the
+    same bits, fewer pixels read. frames [B, H, W, 3] uint8 with records [B, n, 8] (detection_records)
+    also blends every mask into the frame as utils/plot.py:148-152 does, detection by detection:
+    overlay = uint8(0.5 colour + 0.5 pixel), colour = palette[min(class id, len(palette) - 1)]; palette
+    [n_colours, 3] uint8 (None: TAB10). Rectangles and text are the caller's to draw from the records.
+    `out`: caller-owned FrameMasks buffers (overlay may be None without frames); with them and a device
+    palette a call allocates nothing and never synchronises. Every element is written by every call."""
+    code = _frame_mode(mode)
+    for t, name, dt in ((masks, "masks", torch.float32), (counts, "counts", torch.int32)) + \
+            (((det, "det", torch.int64), (box, "box", torch.float32)) if det is not None or box is not None else ()) + \
+            (((frames, "frames", torch.uint8), (records, "records", torch.float32)) if frames is not None else ()) + \
+            (((palette, "palette", torch.uint8),) if palette is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"frame_masks: {name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype != dt:
+            raise ValueError(f"frame_masks: {name} must be {dt}, got {t.dtype}")
+    if len(size) != 2 or int(size[0]) < 1 or int(size[1]) < 1:
+        raise ValueError(f"frame_masks: size must be (H, W) with H, W >= 1, got {size}")
+    H, W = int(size[0]), int(size[1])
+    if masks.dim() != 4 or counts.dim() != 1 or counts.shape[0] != masks.shape[0]:
+        raise ValueError(f"frame_masks: need masks [B, n, mh, mw] and counts [B], got {list(masks.shape)}, "
+                         f"{list(counts.shape)}")
+    B, n, mh, mw = masks.shape
+    if mh < 1 or mw < 1:
+        raise ValueError(f"frame_masks: masks must be [B, n, mh, mw] with mh, mw >= 1, got {list(masks.shape)}")
+    if det is not None and (tuple(det.shape) != (B, n) or box.dim() != 3 or box.shape[0] != B or box.shape[1] < 1
+                            or box.shape[2] != 4):
+        raise ValueError(f"frame_masks: need det [{B}, {n}] and box [{B}, A, 4], got {list(det.shape)}, "
+                         f"{list(box.shape)}")
+    if frames is not None and (tuple(frames.shape) != (B, H, W, 3) or tuple(records.shape) != (B, n, REC)):
+        raise ValueError(f"frame_masks: need frames [{B}, {H}, {W}, 3] and records [{B}, {n}, {REC}], got "
+                         f"{list(frames.shape)}, {list(records.shape)}")
+    if palette is not None and (palette.dim() != 2 or palette.shape[0] < 1 or palette.shape[1] != 3):
+        raise ValueError(f"frame_masks: palette must be [n_colours >= 1, 3], got {list(palette.shape)}")
+    _lib.require_gpu()
+    dev = masks.device
+    if frames is not None and palette is None:
+        palette = TAB10.to(dev)
+    for t, name in ((masks, "masks"), (counts, "counts"), (det, "det"), (box, "box"), (frames, "frames"),
+                    (records, "records"), (palette if frames is not None else None, "palette")):
+        if t is None:
+            continue
+        if not t.is_cuda or t.device != dev:
+            raise ValueError(f"frame_masks: {name} is on {t.device}; every tensor must be on one CUDA device")
+        if not t.is_contiguous():
+            raise ValueError(f"frame_masks: {name} must be contiguous")
+    ob, oa, oo = (None, None, None) if out is None else out
+    bits = _frame_out(ob, (B, n, H, (W + 31) // 32), torch.uint32, dev, "bits")
+    area = _frame_out(oa, (B, n), torch.int32, dev, "area")
+    overlay = None if frames is None else _frame_out(oo, (B, H, W, 3), torch.uint8, dev, "overlay")
+    if B * n == 0:  # nothing is launched: the overlay is the frame
+        if overlay is not None:
+            overlay.copy_(frames)
+        return FrameMasks(bits, area, overlay)
+
+    def vp(t):
+        return None if t is None else ctypes.c_void_p(t.data_ptr())
+    _lib.check(_lib.lib().tv_yolact_frame_masks(
+        vp(masks), mh, mw, vp(counts), B, n, H, W, code, 0 if det is None else 1, vp(det), vp(box),
+        0 if box is None else box.shape[1], vp(frames), vp(records) if frames is not None else None,
+        vp(palette) if frames is not None else None, palette.shape[0] if frames is not None else 0, vp(bits), vp(area),
+        vp(overlay), _lib.stream_of(dev)), "frame_masks")
+    return FrameMasks(bits, area, overlay)
+
+
+def unpack_frame_masks(bits: torch.Tensor, W: int) -> torch.Tensor:
+    """bits [..., H, ceil(W / 32)] (uint32 or int32, host or device) -> bool [..., H, W]: the
+    reference's `mask > 0.5` array. Plain torch ops."""
+    W = int(W)
+    if not isinstance(bits, torch.Tensor) or bits.dtype not in (torch.uint32, torch.int32) or bits.dim() < 2:
+        raise ValueError("unpack_frame_masks: bits must be a uint32 / int32 tensor [..., H, ceil(W / 32)]")
+    if W < 1 or bits.shape[-1] != (W + 31) // 32:
+        raise ValueError(f"unpack_frame_masks: {bits.shape[-1]} words per row do not hold W = {W} pixels")
+    words = bits.contiguous().view(torch.int32).unsqueeze(-1)
+    shifts = torch.arange(32, dtype=torch.int32, device=bits.device)
+    px = ((words >> shifts) & 1).ne(0)  # (an arithmetic shift: the sign fill never reaches bit 0)
+    return px.reshape(*bits.shape[:-1], bits.shape[-1] * 32)[..., :W]
+
+
+def pack_frame_masks(mask: torch.Tensor) -> torch.Tensor:
+    """bool [..., H, W] -> bits [..., H, ceil(W / 32)] uint32 in frame_masks' layout (the inverse of
+    unpack_frame_masks; plain torch ops, for references and tests)."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.dim() < 2:
+        raise ValueError("pack_frame_masks: mask must be a bool tensor [..., H, W]")
+    W = mask.shape[-1]
+    ww = (W + 31) // 32
+    m = torch.zeros(mask.shape[:-1] + (ww * 32,), dtype=torch.int64, device=mask.device)
+    m[..., :W] = mask
+    weights = torch.ones(32, dtype=torch.int64, device=mask.device) << torch.arange(32, device=mask.device)
+    words = (m.reshape(mask.shape[:-1] + (ww, 32)) * weights).sum(-1)  # < 2^32
+    return (words - ((words >> 31) << 32)).to(torch.int32).view(torch.uint32)
+
+
+class DeviceFrameMasks:
+    """Static-buffer frame_masks for a fixed (B, K) and frame size, as DeviceLocalizer: a call launches
+    on the current stream into the preallocated `bits` [B, K, H, ceil(W / 32)], `area` [B, K] and
+    `overlay` [B, H, W, 3] (overlay=False: none is held and no frames are taken), with no allocation
+    and no host synchronisation, so it captures in a graph behind the detector's other steps. `palette`:
+    [n_colours, 3] uint8 (None: TAB10), copied to the device once."""
+
+    def __init__(self, B, K, frame_hw, device, overlay=True, palette=None):
+        if int(B) < 0 or int(K) < 0 or len(frame_hw) != 2 or min(int(v) for v in frame_hw) < 1:
+            raise ValueError(f"DeviceFrameMasks needs B, K >= 0 and frame_hw = (H, W), got {B}, {K}, {frame_hw}")
+        self.B, self.K = int(B), int(K)
+        self.frame_hw = (int(frame_hw[0]), int(frame_hw[1]))
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"DeviceFrameMasks needs a GPU device, got {self.device}")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        H, W = self.frame_hw
+        dev = self.device
+        self.bits = torch.zeros((self.B, self.K, H, (W + 31) // 32), dtype=torch.uint32, device=dev)
+        self.area = torch.zeros((self.B, self.K), dtype=torch.int32, device=dev)
+        self.overlay = torch.zeros((self.B, H, W, 3), dtype=torch.uint8, device=dev) if overlay else None
+        pal = TAB10 if palette is None else palette
+        if not isinstance(pal, torch.Tensor) or pal.dtype != torch.uint8 or pal.dim() != 2 or pal.shape[0] < 1 \
+                or pal.shape[1] != 3:
+            raise ValueError("DeviceFrameMasks: palette must be a uint8 [n_colours >= 1, 3] tensor")
+        self.palette = pal.to(dev).contiguous()
+        self._host = None
+
+    def __call__(self, masks, counts, mode="bilinear", det=None, box=None, frames=None, records=None) -> FrameMasks:
+        """frame_masks into the static buffers; frames (with records) only when built with overlay."""
+        if frames is not None and self.overlay is None:
+            raise ValueError("DeviceFrameMasks was built with overlay=False: it takes no frames")
+        if not isinstance(masks, torch.Tensor) or masks.dim() != 4 or tuple(masks.shape[:2]) != (self.B, self.K):
+            raise ValueError(f"DeviceFrameMasks built for masks [{self.B}, {self.K}, mh, mw]")
+        return frame_masks(masks, counts, self.frame_hw, mode, det, box, frames, records,
+                           self.palette if frames is not None else None,
+                           FrameMasks(self.bits, self.area, self.overlay if frames is not None else None))
+
+    def host(self, overlay=True) -> FrameMasks:
+        """The last call's (bits, area, overlay or None) on the host: copied to pinned memory, one
+        synchronisation. Views of this object's pinned mirror, overwritten by the next host()."""
+        srcs = [self.bits.view(-1).view(torch.uint8), self.area.view(-1).view(torch.uint8)]
+        if overlay and self.overlay is not None:
+            srcs.append(self.overlay.view(-1))
+        if self._host is None:
+            total = self.bits.numel() * 4 + self.area.numel() * 4 + (0 if self.overlay is None else self.overlay.numel())
+            self._host = torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=True)
+        parts, off = [], 0
+        with torch.cuda.device(self.device):
+            for s in srcs:
+                parts.append(self._host[off:off + s.numel()])
+                parts[-1].copy_(s, non_blocking=True)
+                off += s.numel()
+            torch.cuda.current_stream(self.device).synchronize()
+        return FrameMasks(parts[0].view(torch.uint32).view(self.bits.shape),
+                          parts[1].view(torch.int32).view(self.area.shape),
+                          parts[2].view(self.overlay.shape) if len(parts) > 2 else None)
+
+
 # ---- the neck and the head: everything of Yolact.forward after the backbone (model.py:34-60) ----
 
 def yolact_head_state_dict(state_dict):
@@ -721,7 +918,7 @@ class Yolact(YolactHead):
         super().invalidate()
         self._detectors = {}
 
-    def detect(self, frames, top_k, iou_threshold, confidence_threshold, depth=None, camera=None):
+    def detect(self, frames, top_k, iou_threshold, confidence_threshold, depth=None, camera=None, frame_masks=None):
         """The node's callback from the camera frame to the detections (yolact_node.py:109-143) in one
         call: uint8 RGB frames [B, H, W, 3] (or [H, W, 3]) of any size, resized to (config.in_h,
         config.in_w), through a cached YolactDetector (native backbone). depth (uint16 millimetres,
@@ -729,7 +926,9 @@ class Yolact(YolactHead):
         detection (:177-193). Returns YolactDetections(records [B, K, 8] and counts [B] on the host,
         the masks [B, K, 4h, 4w] on the device — the detector's static buffer, overwritten by the next
         call —, points [B, K, 8] on the host or None); K = min(top_k, anchors). One device-to-host
-        synchronisation."""
+        synchronisation. frame_masks = "bilinear" or "nearest" also gives the masks at the frames' own
+        size (YolactDetector's frame_masks step): bits, area and overlay, on the device like `masks`
+        (the detector's static buffers; `unpack_frame_masks(bits, W)` is the reference's bool array)."""
         from .localize import _host_depth
         frames, _ = _frames(frames, None, self.config)
         if int(top_k) < 1:
@@ -740,31 +939,39 @@ class Yolact(YolactHead):
             raise ValueError(f"camera must be (fx, fy, cx, cy), got {camera}")
         if not self._native():
             raise ValueError("detect needs the native backbone: Yolact(config, backbone=Resnet101Backbone(config))")
+        if frame_masks is not None:
+            _frame_mode(frame_masks)
         B = frames.shape[0]
         if depth is not None:
             depth = _host_depth(depth, max(B, 1))
         frames = _frames_on_gpu(frames)
         dev = frames.device
         hw, size = (frames.shape[1], frames.shape[2]), (int(self.config.in_h), int(self.config.in_w))
-        key = (dev.index, B, hw, size, int(top_k), self.precision, self._version_key())
+        key = (dev.index, B, hw, size, int(top_k), self.precision, self._version_key(), frame_masks)
         det = getattr(self, "_detectors", {}).get(key)
         if det is None:
-            det = YolactDetector(self, B, hw, int(top_k), dev, size)
+            det = YolactDetector(self, B, hw, int(top_k), dev, size, frame_masks=frame_masks)
             self._detectors = {key: det}
         res = det(frames, iou_threshold, confidence_threshold, None if depth is None else depth.to(dev), camera)
         records, counts, points = det.host()
-        return YolactDetections(records.clone(), counts.clone(), res.masks, None if points is None else points.clone())
+        return YolactDetections(records.clone(), counts.clone(), res.masks, None if points is None else points.clone(),
+                                res.bits, res.area, res.overlay)
 
 
 class YolactDetections(NamedTuple):
     """records [B, K, 8] fp32 (anchor, class id, its probability, foreground confidence, y, x, h, w;
     rows at or past counts[b] zero), counts [B] int32, masks [B, K, 4h, 4w] fp32 on the device (rows
     past counts[b] are not written), points [B, K, 8] fp32 (DeviceLocalizer's x, y, z, valid, n_pixels,
-    depth_sum, e_x, e_y) or None without depth."""
+    depth_sum, e_x, e_y) or None without depth. With the detector's frame_masks step: bits [B, K, H,
+    ceil(W / 32)] uint32, area [B, K] int32 and overlay [B, H, W, 3] uint8 (None for the fp32 entry) of
+    FrameMasks at the frame size, on the device; None without it."""
     records: torch.Tensor
     counts: torch.Tensor
     masks: torch.Tensor
     points: Optional[torch.Tensor]
+    bits: Optional[torch.Tensor] = None
+    area: Optional[torch.Tensor] = None
+    overlay: Optional[torch.Tensor] = None
 
 
 class YolactDetector:
@@ -773,7 +980,10 @@ class YolactDetector:
     assemble_masks_indexed -> detection_records and, with depth, DeviceLocalizer.masks(bound_by_box).
     `model`: a Yolact on the native backbone; frame_hw = (H, W) of the camera frames; size = (in_h,
     in_w) of the model (None: the frames' own size; another size runs `preprocess` into a static fp32
-    image first); K = min(top_k, anchors).
+    image first); K = min(top_k, anchors). frame_masks = "bilinear" or "nearest" adds the masks at
+    frame_hw after detection_records (DeviceFrameMasks `frame`, bounded by the boxes): bits and area,
+    and the overlay onto the uint8 frames of the call (the fp32 entry has no frames: overlay None).
+    With None (the default) the step does not exist: no launch, no buffer.
 
     A call launches on the current stream, allocates nothing and never synchronises, so it can be
     captured in a graph after one eager call on the capture stream (the pattern of YolactHead(out=...)).
@@ -782,8 +992,10 @@ class YolactDetector:
     `counts` [B] as views of one allocation `packed` (DeviceDecoder's layout: one copy carries both) —
     are overwritten by every call. Mask rows past counts[b] are not written (they start as zeros)."""
 
-    def __init__(self, model, B, frame_hw, top_k, device, size=None):
+    def __init__(self, model, B, frame_hw, top_k, device, size=None, frame_masks=None):
         from .localize import DeviceLocalizer
+        if frame_masks is not None:
+            _frame_mode(frame_masks)
         if not isinstance(model, Yolact) or not model._native():
             raise ValueError("YolactDetector needs a Yolact on the native backbone "
                              "(Yolact(config, backbone=Resnet101Backbone(config)))")
@@ -816,6 +1028,9 @@ class YolactDetector:
         self.masks = torch.zeros((self.B, K, ph, pw), dtype=torch.float32, device=dev)
         self.localizer = DeviceLocalizer(self.B, K, dev)
         self.points = self.localizer.out
+        self.frame_mode = frame_masks
+        self.frame = None if frame_masks is None else DeviceFrameMasks(self.B, K, self.frame_hw, dev)
+        self._overlaid = False
         self._localized = False
         self._host = None
 
@@ -836,6 +1051,7 @@ class YolactDetector:
             if tuple(frames.shape) != (self.B, 3) + self.size:
                 raise ValueError(f"the fp32 image must be {[self.B, 3, *self.size]}, got {list(frames.shape)}")
             pred = m.forward(frames, out=self.head_out)
+            u8 = None
         else:
             frames, _ = _frames(frames, None, m.config)
             if tuple(frames.shape) != (self.B,) + self.frame_hw + (3,):
@@ -844,6 +1060,7 @@ class YolactDetector:
                 pred = m.forward_frames(frames, out=self.head_out)
             else:
                 pred = m.forward(preprocess(frames, self.size[0], self.size[1], out=self.img), out=self.head_out)
+            u8 = frames
         classification, box_encoding, mask_coeff, anchor, mask_prototype = pred
         box = box_decode(box_encoding, anchor, m.config, out=self.box)
         det, counts = self.nms(classification, box, iou_threshold, confidence_threshold)
@@ -853,7 +1070,19 @@ class YolactDetector:
         if self._localized:
             fx, fy, cx, cy = camera
             self.localizer.masks(self.masks, counts, det, box, depth, fx, fy, cx, cy, bound_by_box=True)
-        return YolactDetections(self.records, self.counts, self.masks, self.points if self._localized else None)
+        points = self.points if self._localized else None
+        if self.frame is None:
+            return YolactDetections(self.records, self.counts, self.masks, points)
+        self._overlaid = u8 is not None
+        fm = self.frame(self.masks, counts, self.frame_mode, det, box, u8, None if u8 is None else self.records)
+        return YolactDetections(self.records, self.counts, self.masks, points, fm.bits, fm.area, fm.overlay)
+
+    def host_frame_masks(self) -> FrameMasks:
+        """FrameMasks(bits, area, overlay or None) of the last call on the host: copied to pinned memory
+        with one synchronisation; views of the pinned mirror, overwritten by the next call of this."""
+        if self.frame is None:
+            raise ValueError("this YolactDetector was built without frame_masks")
+        return self.frame.host(overlay=self._overlaid)
 
     def host(self):
         """(records [B, K, 8], counts [B], points [B, K, 8] or None) of the last call on the host: the
