@@ -304,6 +304,39 @@ int tv_decode(const float* heat, const int64_t heat_strides[4], const float* siz
               const float* aux, const int64_t aux_strides[5], float* records, int32_t* counts, void* workspace,
               int64_t workspace_bytes, void* stream);
 
+/* Roll, pitch and yaw of the detections tv_decode wrote: the reference's angle_decode (decode.py:291-316,
+ * the inverse of angle_loss's encoding, loss.py:334-376) evaluated at the records' peaks only — the step
+ * its decode() leaves as "TODO: Decode angles". One small launch after tv_decode; device pointers, async
+ * on `stream`, no workspace, no host synchronisation (graph-capturable).
+ * records [B, K, rec_stride] fp32 (rec_stride >= 8) with counts [B] int32 (clamped to [0, K]), as written by
+ * tv_decode in either mode: label, y and x of a record come from its flat peak index in column 7
+ * (label*H*W + y*W + x, exact in fp32 while C*H*W < 2^24; TV_EINVAL otherwise).
+ * Per axis, in Prediction order roll, pitch, yaw: the bin head and the offset head, [B, H, W, 4] fp32 views
+ * with element strides[4] ([outside, inside] logits of bin 0 then bin 1; [sin, cos] offsets of bin 0 then
+ * bin 1). Both pointers NULL: the head is absent. theta_range [3, C] fp32 on the device: the period of
+ * axis a for label c (ObjectConfig.{roll,pitch,yaw}.modulo), NaN = not decoded for this label.
+ * Per record and axis, in fp32, with b the four logits and o the four offsets at (b, y, x):
+ *   s0 = softmax(b[0:2])[1], s1 = softmax(b[2:4])[1]; bin 1 is used when s1 > s0 (strict, on the fp32
+ *   scores: two scores saturated to 1.0f choose bin 0);
+ *   angle = use1 ? -pi/2 + atan2(o[2], o[3]) : pi/2 + atan2(o[0], o[1]);
+ *   angles = remainder(angle, 2 pi) * (theta_range / (2 pi))      (torch.remainder: in [0, 2 pi))
+ * The training bins' overlap does not enter the decode.
+ * Output angles [B, K, 3] fp32 (roll, pitch, yaw), every element written by every call: NaN for rows
+ * d >= counts[b], for an absent head, for a NaN theta_range, and for a flat index outside [0, C*H*W).
+ * Packed layout (the Python DeviceDecoder's `packed`, the buffer RecordGather gathers): one allocation of
+ * 4-byte elements — records [B, K, 10] fp32, then counts [B] int32, then, with the angles option, angles
+ * [B, K, 3] fp32 — so one device-to-host copy or one collective carries all three; without the option the
+ * buffer ends after the counts.
+ * TV_EINVAL before any launch: null records, counts, theta_range or angles; rec_stride < 8; a bin head
+ * without its offset head or the reverse; a present head without strides; non-positive C, H, W or K; B < 0;
+ * C*H*W >= 2^24. B == 0 succeeds and launches nothing. */
+int tv_decode_angles(const float* records, int32_t rec_stride, const int32_t* counts, const float* roll_bin,
+                     const int64_t roll_bin_strides[4], const float* roll_offset, const int64_t roll_offset_strides[4],
+                     const float* pitch_bin, const int64_t pitch_bin_strides[4], const float* pitch_offset,
+                     const int64_t pitch_offset_strides[4], const float* yaw_bin, const int64_t yaw_bin_strides[4],
+                     const float* yaw_offset, const int64_t yaw_offset_strides[4], const float* theta_range, int32_t B,
+                     int32_t C, int32_t H, int32_t W, int32_t K, float* angles, void* stream);
+
 /* YOLACT post-processing (reference src/tauv_vision/yolact/model/), fp32,
  * device pointers, async on `stream`.
  * box_decode (boxes.py:55-61): enc [B,A,4] (y, x, h, w encodings), anchor [anchor_batch,A,4]

@@ -631,6 +631,35 @@ int tv_decode(const float* heat, const int64_t hs[4], const float* size, const i
   })
 }
 
+int tv_decode_angles(const float* records, int32_t rec_stride, const int32_t* counts, const float* roll_bin,
+                     const int64_t roll_bin_strides[4], const float* roll_offset, const int64_t roll_offset_strides[4],
+                     const float* pitch_bin, const int64_t pitch_bin_strides[4], const float* pitch_offset,
+                     const int64_t pitch_offset_strides[4], const float* yaw_bin, const int64_t yaw_bin_strides[4],
+                     const float* yaw_offset, const int64_t yaw_offset_strides[4], const float* theta_range, int32_t B,
+                     int32_t C, int32_t H, int32_t W, int32_t K, float* angles, void* stream) {
+  TV_GUARD({
+    AngleParams p{};
+    p.records = records; p.rec_stride = rec_stride; p.counts = counts;
+    const float* bins[3] = {roll_bin, pitch_bin, yaw_bin};
+    const float* offs[3] = {roll_offset, pitch_offset, yaw_offset};
+    const int64_t* bst[3] = {roll_bin_strides, pitch_bin_strides, yaw_bin_strides};
+    const int64_t* ost[3] = {roll_offset_strides, pitch_offset_strides, yaw_offset_strides};
+    for (int a = 0; a < 3; ++a) {
+      p.bin[a] = bins[a];
+      p.off[a] = offs[a];
+      if ((bins[a] && !bst[a]) || (offs[a] && !ost[a])) { set_error("decode_angles: head strides missing"); return TV_EINVAL; }
+      for (int i = 0; i < 4; ++i) {
+        p.bin_st[a][i] = bins[a] ? bst[a][i] : 0;
+        p.off_st[a][i] = offs[a] ? ost[a][i] : 0;
+      }
+    }
+    p.theta_range = theta_range;
+    p.B = B; p.C = C; p.H = H; p.W = W; p.K = K;
+    p.angles = angles;
+    return launch_decode_angles(p, (hipStream_t)stream);
+  })
+}
+
 int tv_diag_dcn_conv(const void* x, const void* om, int32_t B, int32_t H, int32_t W, int32_t C, int32_t om_ldc,
                      const float* weight, const float* bias, int32_t N, int32_t act, int32_t dtype, int32_t variant,
                      void* out, void* stream) {

@@ -527,5 +527,19 @@ int launch_decode(const float* heat, const int64_t st[4], int B, int C, int H, i
 // heatmap_detect()'s (index[B,K,2], label[B,K]) as int64 from flat top-K indices.
 int launch_index_split(const int32_t* flat, int B, int K, int H, int W, int64_t* index, int64_t* label,
                        hipStream_t s);
+// tv_decode_angles: roll / pitch / yaw of every detection record (passed by value to the kernel).
+struct AngleParams {
+  const float* records;      // [B][K][rec_stride], flat peak index in column 7
+  int rec_stride;
+  const int32_t* counts;     // [B]
+  const float* bin[3];       // roll, pitch, yaw: [B,H,W,4] views, null = head absent
+  const float* off[3];
+  int64_t bin_st[3][4], off_st[3][4];
+  const float* theta_range;  // [3][C], NaN = not decoded for this label
+  int B, C, H, W, K;
+  float* angles;             // [B][K][3]
+};
+// Validates (returns 1 = TV_EINVAL before any launch) and launches decode_angles_kernel (decode.hip).
+int launch_decode_angles(const AngleParams& p, hipStream_t s);
 
 }  // namespace tv

@@ -1295,4 +1295,91 @@ int launch_index_split(const int32_t* flat, int B, int K, int H, int W, int64_t*
   return 0;
 }
 
+// ---- tv_decode_angles: roll / pitch / yaw of the detection records ------------------------------
+// angle_decode (decode.py:291-316) at the records' peaks only: one thread per record (b, d), per axis
+// the four bin logits and four offsets at (b, y, x) of the record's flat index, all in fp32 in the
+// reference's operation order. Every element of angles [B][K][3] is written: NaN for rows past the
+// image's count, for an absent head, for a label whose period is NaN and for a flat index outside
+// [0, C*H*W) (records not written by tv_decode).
+constexpr int kAngleThreads = 256;
+
+// softmax([outside, inside])[1] as torch forms it: exp(x - max) / sum
+__device__ __forceinline__ float inside_score(float outside, float inside) {
+  const float m = fmaxf(outside, inside);
+  const float eo = expf(outside - m), ei = expf(inside - m);
+  return ei / (eo + ei);
+}
+
+__global__ __launch_bounds__(kAngleThreads) void decode_angles_kernel(const AngleParams p) {
+  const int i = blockIdx.x * kAngleThreads + threadIdx.x;
+  if (i >= p.B * p.K) return;
+  const int b = i / p.K, d = i - b * p.K;
+  const float nan = __builtin_nanf("");
+  float res[3] = {nan, nan, nan};
+  const int n = min(max(p.counts[b], 0), p.K);
+  const float f = d < n ? p.records[(size_t)i * p.rec_stride + 7] : -1.f;
+  const int hw = p.H * p.W;
+  if (f >= 0.f && f < (float)(p.C * hw)) {  // (C*H*W < 2^24: exact in fp32)
+    const int idx = (int)f;
+    const int label = idx / hw;
+    const int rem = idx - label * hw;
+    const int iy = rem / p.W;
+    const int ix = rem - iy * p.W;
+    // the loads of every decoded axis first, then the arithmetic
+    float tr[3], bl[3][4], of[3][4];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      tr[a] = p.bin[a] ? p.theta_range[a * p.C + label] : nan;
+      if (tr[a] == tr[a]) {
+        const float* pb = p.bin[a] + b * p.bin_st[a][0] + iy * p.bin_st[a][1] + ix * p.bin_st[a][2];
+        const float* po = p.off[a] + b * p.off_st[a][0] + iy * p.off_st[a][1] + ix * p.off_st[a][2];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          bl[a][c] = pb[c * p.bin_st[a][3]];
+          of[a][c] = po[c * p.off_st[a][3]];
+        }
+      }
+    }
+    const float two_pi = (float)(2.0 * M_PI), half_pi = (float)(M_PI / 2.0);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      if (!(tr[a] == tr[a])) continue;
+      const float s0 = inside_score(bl[a][0], bl[a][1]), s1 = inside_score(bl[a][2], bl[a][3]);
+      const float ang = s1 > s0 ? -half_pi + atan2f(of[a][2], of[a][3]) : half_pi + atan2f(of[a][0], of[a][1]);
+      float m = fmodf(ang, two_pi);  // torch.remainder: the sign of the divisor
+      if (m != 0.f && m < 0.f) m += two_pi;
+      res[a] = m * (float)((double)tr[a] / (2.0 * M_PI));
+    }
+  }
+  float* out = p.angles + (size_t)i * 3;
+  out[0] = res[0];
+  out[1] = res[1];
+  out[2] = res[2];
+}
+
+int launch_decode_angles(const AngleParams& p, hipStream_t s) {
+  if (!p.records || !p.counts || !p.theta_range || !p.angles) { set_error("decode_angles: null pointer"); return 1; }
+  if (p.rec_stride < 8) { set_error("decode_angles: rec_stride must be >= 8 (flat index in column 7)"); return 1; }
+  for (int a = 0; a < 3; ++a)
+    if ((p.bin[a] == nullptr) != (p.off[a] == nullptr)) {
+      set_error("decode_angles: a bin head and its offset head go together");
+      return 1;
+    }
+  if (p.C < 1 || p.H < 1 || p.W < 1 || p.K < 1) { set_error("decode_angles: C, H, W, K must be positive"); return 1; }
+  if (p.B < 0) { set_error("decode_angles: negative B"); return 1; }
+  if ((int64_t)p.C * p.H * p.W >= (int64_t)1 << 24) {
+    set_error("decode_angles: C*H*W must be below 2^24 (the flat index is read from an fp32 column)");
+    return 1;
+  }
+  if ((int64_t)p.B * p.K > (int64_t)0x7FFFFFFF - kAngleThreads) {  // (the kernel's thread index is an int)
+    set_error("decode_angles: B*K too large");
+    return 1;
+  }
+  if (p.B == 0) return 0;
+  const unsigned blocks = (unsigned)(((int64_t)p.B * p.K + kAngleThreads - 1) / kAngleThreads);
+  hipLaunchKernelGGL(decode_angles_kernel, dim3(blocks), dim3(kAngleThreads), 0, s, p);
+  TV_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace tv

@@ -6,9 +6,10 @@ from .config import AngleConfig, ModelConfig, ObjectConfig, ObjectConfigSet, Tra
 from .centernet import (CenterpointDLA34, Centernet, CenternetDetections, CenternetDetector, Prediction,  # noqa: F401
                         get_head_channels, initialize_weights, preprocess)
 from .dla import DLABackbone  # noqa: F401
-from .decode import (Detection, DeviceKeypointDecoder, KeypointDetection, KeypointRecords, angle_decode,  # noqa: F401
-                     angle_get_bins, decode, decode_keypoints, decode_keypoints_records, decode_records, depth_decode,
-                     heatmap_detect, heatmap_nms, keypoint_detections_from_records)
+from .decode import (Detection, DeviceAngleDecoder, DeviceDecoder, DeviceKeypointDecoder,  # noqa: F401
+                     KeypointDetection, KeypointRecords, angle_decode, angle_get_bins, angle_ranges, decode,
+                     decode_keypoints, decode_keypoints_records, decode_oriented, decode_oriented_records,
+                     decode_records, depth_decode, heatmap_detect, heatmap_nms, keypoint_detections_from_records)
 from .yolact import (DeviceFrameMasks, FeaturePyramid, FrameMasks, Masknet, PredictionHead,  # noqa: F401
                      Resnet101Backbone, TAB10, Yolact, YolactConfig, YolactDetections, YolactDetector, YolactHead,
                      detection_records, frame_masks, pack_frame_masks, unpack_frame_masks, yolact_head_state_dict)

@@ -119,6 +119,8 @@ EXPORTS = {
     "tv_decode": ([c_vp, ctypes.POINTER(c_i64), c_vp, ctypes.POINTER(c_i64), c_vp, ctypes.POINTER(c_i64), c_vp,
                    ctypes.POINTER(c_i64), c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp,
                    ctypes.POINTER(c_i64), c_vp, c_vp, c_vp, c_i64, c_vp], c_i32),
+    "tv_decode_angles": ([c_vp, c_i32, c_vp] + [c_vp, ctypes.POINTER(c_i64)] * 6 +
+                         [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp], c_i32),
     "tv_yolact_box_decode": ([c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp], c_i32),
     "tv_yolact_box_encode": ([c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp], c_i32),
     "tv_yolact_fast_nms": ([c_vp, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp], c_i32),

@@ -192,12 +192,17 @@ class _NativeModel(NativeModule):
             return prediction_from_nhwc(self._launch(eng, "u8", frames), self.object_config)
         return prediction_from_nhwc(self._launch(eng, "f32", preprocess(frames, in_h, in_w)), self.object_config)
 
-    def detect(self, frames: torch.Tensor, model_config, n_detections: int = 100, score_threshold: float = 0.3):
+    def detect(self, frames: torch.Tensor, model_config, n_detections: int = 100, score_threshold: float = 0.3,
+               angles: bool = False):
         """detect(frames) == decode(forward(preprocess(frames)), ...): camera frames of any size,
-        resized to (model_config.in_h, model_config.in_w) like the node."""
-        from .decode import decode
-        return decode(self.forward_frames(frames, (model_config.in_h, model_config.in_w)), model_config,
-                      n_detections, score_threshold)
+        resized to (model_config.in_h, model_config.in_w) like the node. angles=True: decode_oriented
+        with the model's own object config, so Detection.roll / .pitch / .yaw are filled for the labels
+        that train them."""
+        from .decode import decode, decode_oriented
+        pred = self.forward_frames(frames, (model_config.in_h, model_config.in_w))
+        if angles:
+            return decode_oriented(pred, model_config, self.object_config, n_detections, score_threshold)
+        return decode(pred, model_config, n_detections, score_threshold)
 
     def detect_keypoints(self, frames, model_config, n_detections: int = 10, keypoint_n_detections: int = 50,
                          score_threshold: float = 0.6, keypoint_score_threshold: float = 0.3, depth=None, camera=None,

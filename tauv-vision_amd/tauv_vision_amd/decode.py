@@ -13,6 +13,9 @@ Differences from the reference:
   * top-K ties are broken toward the smaller flat index (torch.topk: unspecified).
   * label / y / x use integer division (== the reference's float32 division, decode.py:271-277,
     while C*H*W < 2^24).
+  * decode() leaves Detection.roll / pitch / yaw at None, as the reference's does ("TODO: Decode angles",
+    decode.py:193-202); decode_oriented() / decode_oriented_records() fill them by the reference's
+    angle_decode at the detections' peaks (tv_decode_angles, one launch after the decode).
 """
 import ctypes
 import threading
@@ -111,9 +114,12 @@ class DeviceDecoder:
     """Static-buffer decode for a fixed (B, C, H, W, K): launches sigmoid+NMS, exact top-K
     and the record gather on the current stream into preallocated device buffers, with no
     host synchronisation — so a forward + decode step can be captured in a HIP graph.
-    `records` is [B, K, 10] fp32, `counts` [B] int32 (see include/tauv_vision_amd.h)."""
+    `records` is [B, K, 10] fp32, `counts` [B] int32 (see include/tauv_vision_amd.h).
+    angles=True appends an `angles` section [B, K, 3] fp32 (roll, pitch, yaw) to `packed`, after the
+    counts, for a DeviceAngleDecoder to write (the decode itself never touches it); the prefix layout
+    is the same either way."""
 
-    def __init__(self, B, C, H, W, K, device):
+    def __init__(self, B, C, H, W, K, device, angles=False):
         if not 1 <= K <= C * H * W:
             raise RuntimeError(f"selected index k out of range (k={K}, n={C * H * W})")
         self.shape = (B, C, H, W, K)
@@ -122,11 +128,13 @@ class DeviceDecoder:
         _lib.check(_lib.lib().tv_decode_workspace_size(B, C, H, W, K, ctypes.byref(need)), "decode")
         self.ws_bytes = need.value
         self.ws = torch.zeros(need.value, dtype=torch.uint8, device=self.device)  # counters zero-filled (tv_decode keeps them so)
-        # records and counts in one allocation (`packed`): a single D2H copy carries both
+        # records and counts (then the angles) in one allocation (`packed`): a single D2H copy carries all
         nrec = B * K * REC
-        self.packed = torch.empty((nrec + B) * 4, dtype=torch.uint8, device=self.device)
+        nang = B * K * 3 if angles else 0
+        self.packed = torch.empty((nrec + B + nang) * 4, dtype=torch.uint8, device=self.device)
         self.records = self.packed[:nrec * 4].view(torch.float32).view(B, K, REC)
-        self.counts = self.packed[nrec * 4:].view(torch.int32)
+        self.counts = self.packed[nrec * 4:(nrec + B) * 4].view(torch.int32)
+        self.angles = self.packed[(nrec + B) * 4:].view(torch.float32).view(B, K, 3) if angles else None
 
     def __call__(self, heat, size, offset, depth, mode, ratio, in_h, in_w, thr, aux=None):
         B, C, H, W, K = self.shape
@@ -152,19 +160,96 @@ class DeviceDecoder:
         return self.records, self.counts
 
 
-_DECODERS = {}  # (device, B, C, H, W, K) -> (DeviceDecoder, pinned host mirror of its packed buffer)
+ANGLE_AXES = ("roll", "pitch", "yaw")  # Prediction order; the columns of `angles`
+
+
+def angle_ranges(object_config) -> np.ndarray:
+    """float32 [3, n_labels]: the period of roll / pitch / yaw for each label, as the reference's
+    angle_range takes it from ObjectConfig.{roll,pitch,yaw}.modulo (loss.py:151-175) — NaN ("not decoded")
+    where the label's AngleConfig.train is false or its modulo is None."""
+    out = np.full((3, object_config.n_labels), np.nan, dtype=np.float32)
+    for a, axis in enumerate(ANGLE_AXES):
+        for c, cfg in enumerate(object_config.configs):
+            ac = getattr(cfg, axis)
+            if ac.train and ac.modulo is not None:
+                out[a, c] = ac.modulo
+    return out
+
+
+class DeviceAngleDecoder:
+    """Static-buffer roll / pitch / yaw of a DeviceDecoder's records (tv_decode_angles, csrc/decode.hip):
+    the reference's angle_decode at the records' peaks, one launch on the current stream with no
+    allocation and no host synchronisation, so decode + angles can be captured in one HIP graph. Holds
+    the per-label period table `theta_range` [3, n_labels] (angle_ranges) on the device and `angles`
+    [B, K, 3] fp32 (roll, pitch, yaw; NaN = not decoded: rows past counts[b], an absent head, a label
+    without that angle) — `out`: a caller-owned contiguous buffer for it (a DeviceDecoder's `angles`
+    section). Every element is overwritten by every call."""
+
+    def __init__(self, B, K, object_config, device, out=None):
+        _lib.require_gpu()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"DeviceAngleDecoder needs a GPU device, got {self.device}")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if int(B) < 0 or int(K) < 1:
+            raise ValueError(f"DeviceAngleDecoder needs B >= 0 and K >= 1, got {B}, {K}")
+        self.B, self.K, self.n_labels = int(B), int(K), object_config.n_labels
+        self.theta_range = torch.from_numpy(angle_ranges(object_config)).to(self.device)
+        self.angles = _lib.check_out(out, (self.B, self.K, 3), self.device, "DeviceAngleDecoder")
+
+    def __call__(self, records, counts, prediction):
+        """records [B, K, >= 8] fp32 / counts [B] int32 on the device (DeviceDecoder's), prediction: the
+        Prediction they were decoded from. Returns the device `angles`. ValueError before the launch for
+        host tensors, other shapes than the decoder's, or a heatmap whose channels are not the labels."""
+        B, K = self.B, self.K
+        heat = prediction.heatmap
+        if not isinstance(heat, torch.Tensor) or heat.dim() != 4 or heat.shape[0] != B or heat.shape[1] != self.n_labels:
+            raise ValueError(f"heatmap must be [{B}, {self.n_labels}, H, W], got "
+                             f"{list(heat.shape) if isinstance(heat, torch.Tensor) else type(heat)}")
+        _, C, H, W = heat.shape
+        for name, t, dt in (("records", records, torch.float32), ("counts", counts, torch.int32)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dt} tensor on {self.device}")
+        if records.dim() != 3 or tuple(records.shape[:2]) != (B, K) or tuple(counts.shape) != (B,):
+            raise ValueError(f"records / counts shapes {list(records.shape)} / {list(counts.shape)} != decoder's "
+                             f"{[B, K, REC]} / {[B]}")
+        args = []
+        for axis in ANGLE_AXES:
+            for part in ("bin", "offset"):
+                t = getattr(prediction, f"{axis}_{part}")
+                if t is None:
+                    args += [None, None]
+                    continue
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != self.device \
+                        or tuple(t.shape) != (B, H, W, 4):
+                    raise ValueError(f"{axis}_{part} must be a float32 {[B, H, W, 4]} tensor on {self.device}")
+                args += [ctypes.c_void_p(t.data_ptr()), _lib.strides(t, 4)]
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        _lib.check(_lib.lib().tv_decode_angles(vp(records), records.shape[2], vp(counts), *args, vp(self.theta_range),
+                                               B, C, H, W, K, vp(self.angles), _lib.stream_of(self.device)),
+                   "decode_angles")
+        return self.angles
+
+
+_DECODERS = {}  # (device, B, C, H, W, K, slot, angle table) -> (DeviceDecoder, pinned host mirror, angle decoder)
 _DECODERS_LOCK = threading.Lock()
 _DECODERS_MAX = 8
 
 
-def _decoder(dev, B, C, H, W, K):
-    key = (dev.index, B, C, H, W, K)
+def _decoder(dev, B, C, H, W, K, slot=0, object_config=None):
+    """The cached decoder of a shape; `slot`: which of several decodes of that shape inside one
+    _records_many call (each has its own outputs and host mirror); object_config: with the angle section
+    and its DeviceAngleDecoder (keyed by the period table)."""
+    table = None if object_config is None else angle_ranges(object_config).tobytes()
+    key = (dev.index, B, C, H, W, K, slot, table)
     ent = _DECODERS.get(key)
     if ent is None:
         if len(_DECODERS) >= _DECODERS_MAX:
             _DECODERS.pop(next(iter(_DECODERS)))
-        dec = DeviceDecoder(B, C, H, W, K, dev)
-        ent = (dec, torch.empty(dec.packed.numel(), dtype=torch.uint8, pin_memory=True))
+        dec = DeviceDecoder(B, C, H, W, K, dev, angles=object_config is not None)
+        ang = None if object_config is None else DeviceAngleDecoder(B, K, object_config, dev, out=dec.angles)
+        ent = (dec, torch.empty(dec.packed.numel(), dtype=torch.uint8, pin_memory=True), ang)
         _DECODERS[key] = ent
     return ent
 
@@ -173,24 +258,37 @@ def _records_many(calls):
     """Run several device decodes back to back on the current stream, each into a cached decoder
     (static workspace and records: no allocation or zero fill per call), copy every packed record
     buffer to pinned host memory and synchronise ONCE. calls: (heat, size, offset, depth, K, mode,
-    ratio, in_h, in_w, thr, aux) tuples; returns [(records [B,K,10], counts [B])] host numpy."""
+    ratio, in_h, in_w, thr, aux) tuples, optionally with a 12th element (prediction, object_config):
+    tv_decode_angles follows that decode. Two calls of the same (B, C, H, W, K) get a decoder and a host
+    buffer each. Returns [(records [B,K,10], counts [B])] host numpy, (records, counts, angles [B,K,3])
+    for a call with angles."""
     with _DECODERS_LOCK:
-        outs = []
-        for heat, size, offset, depth, K, mode, ratio, in_h, in_w, thr, aux in calls:
+        outs, seen = [], {}
+        for call in calls:
+            heat, size, offset, depth, K, mode, ratio, in_h, in_w, thr, aux = call[:11]
+            oriented = call[11] if len(call) > 11 else None
             heat = _gpu(heat, "heatmap")
             B, C, H, W = heat.shape
             _empty_batch_check(B)
-            dec, host = _decoder(heat.device, B, C, H, W, K)
+            shape = (heat.device.index, B, C, H, W, K)
+            slot = seen[shape] = seen.get(shape, -1) + 1
+            dec, host, ang = _decoder(heat.device, B, C, H, W, K, slot, None if oriented is None else oriented[1])
             dec(heat, size, offset, depth, mode, ratio, in_h, in_w, thr, aux)
+            if ang is not None:
+                ang(dec.records, dec.counts, oriented[0])
             host.copy_(dec.packed, non_blocking=True)
-            outs.append((host, B, K))
+            outs.append((host, B, K, ang is not None))
         torch.cuda.current_stream(heat.device).synchronize()
         res = []
-        for host, B, K in outs:
+        for host, B, K, has_angles in outs:
             a = host.numpy()
-            records = a[:B * K * REC * 4].view(np.float32).reshape(B, K, REC).copy()
-            counts = a[B * K * REC * 4:].view(np.int32).copy()
-            res.append((records, counts))
+            nrec = B * K * REC
+            records = a[:nrec * 4].view(np.float32).reshape(B, K, REC).copy()
+            counts = a[nrec * 4:(nrec + B) * 4].view(np.int32).copy()
+            if has_angles:
+                res.append((records, counts, a[(nrec + B) * 4:].view(np.float32).reshape(B, K, 3).copy()))
+            else:
+                res.append((records, counts))
         return res
 
 
@@ -215,6 +313,31 @@ def decode(prediction, model_config, n_detections: int, score_threshold: float) 
                                score_threshold)
     from .sharding import records_to_detections
     return records_to_detections(records, counts, has_depth)
+
+
+def decode_oriented_records(prediction, model_config, object_config, n_detections: int, score_threshold: float):
+    """decode_records() plus the orientation of every detection: host numpy records [B, K, 10], counts [B]
+    and angles [B, K, 3] fp32 (roll, pitch, yaw by the reference's angle_decode with the label's period
+    from object_config; NaN where not decoded: rows past counts[b], a prediction without that head, a
+    label that does not train that angle or has no modulo). tv_decode and tv_decode_angles launched back
+    to back, one D2H copy, one host synchronisation."""
+    if object_config.n_labels != prediction.heatmap.shape[1]:
+        raise ValueError(f"the object config has {object_config.n_labels} labels, the heatmap "
+                         f"{prediction.heatmap.shape[1]} channels")
+    return _records_many([(prediction.heatmap, prediction.size, prediction.offset, prediction.depth, n_detections, 0,
+                           model_config.downsample_ratio, model_config.in_h, model_config.in_w, score_threshold, None,
+                           (prediction, object_config))])[0]
+
+
+def decode_oriented(prediction, model_config, object_config, n_detections: int,
+                    score_threshold: float) -> List[List[Detection]]:
+    """decode() with Detection.roll / .pitch / .yaw filled (the reference's "TODO: Decode angles",
+    decode.py:193-202, 222-230): Python floats in [0, modulo) where the label trains the angle and the
+    prediction has the head, None otherwise. Every other field as decode() gives it."""
+    records, counts, angles = decode_oriented_records(prediction, model_config, object_config, n_detections,
+                                                      score_threshold)
+    from .sharding import records_to_detections
+    return records_to_detections(records, counts, prediction.depth is not None, angles)
 
 
 def decode_keypoints(prediction, model_config, object_config, M_projection, n_detections: int,

@@ -30,23 +30,29 @@ class RecordGather:
     decoder's packed buffer (DeviceDecoder.packed: [b_local, K, 10] fp32 records then [b_local]
     int32 counts, one allocation), gathered into a static [world, bytes] buffer (so the step can be
     graph-captured). Each rank contributes exactly `b_local` frames (pad short shards with
-    counts = 0 frames)."""
+    counts = 0 frames). angles=True: the packed buffer of a DeviceDecoder(..., angles=True), which carries
+    [b_local, K, 3] fp32 angles (roll, pitch, yaw) after the counts — the same single collective on the
+    longer buffer; the records-and-counts prefix is laid out the same either way."""
 
-    def __init__(self, b_local: int, k: int, device, group=None):
+    def __init__(self, b_local: int, k: int, device, group=None, angles=False):
         self.group = group
         self.world = dist.get_world_size(group)
         self.device = torch.device(device)
         self.b_local, self.k = b_local, k
         self.nrec = b_local * k * REC
-        self.bytes = (self.nrec + b_local) * 4
+        self.nang = b_local * k * 3 if angles else 0
+        self.bytes = (self.nrec + b_local + self.nang) * 4
         self.buf = torch.empty((self.world, self.bytes), dtype=torch.uint8, device=self.device)
         self._into_tensor = dist.get_backend(group) == "nccl"
 
     @staticmethod
-    def pack(rec: torch.Tensor, cnt: torch.Tensor) -> torch.Tensor:
-        """records [b, K, 10] fp32 + counts [b] int32 -> the packed byte layout (a copy; the device
-        decoder writes this layout in place)."""
-        return torch.cat((rec.contiguous().view(-1).view(torch.uint8), cnt.contiguous().view(-1).view(torch.uint8)))
+    def pack(rec: torch.Tensor, cnt: torch.Tensor, ang: torch.Tensor = None) -> torch.Tensor:
+        """records [b, K, 10] fp32 + counts [b] int32 (+ angles [b, K, 3] fp32) -> the packed byte layout
+        (a copy; the device decoder writes this layout in place)."""
+        parts = [rec.contiguous().view(-1).view(torch.uint8), cnt.contiguous().view(-1).view(torch.uint8)]
+        if ang is not None:
+            parts.append(ang.contiguous().view(-1).view(torch.uint8))
+        return torch.cat(parts)
 
     def __call__(self, packed: torch.Tensor) -> torch.Tensor:
         """packed: this rank's uint8 [bytes] buffer; returns the gathered [world, bytes] buffer."""
@@ -60,24 +66,32 @@ class RecordGather:
 
     def unpack(self, buf: torch.Tensor = None):
         """The gathered buffer (device, or its host copy) -> records [world*b, K, 10] fp32 and counts
-        [world*b] int32, frames in rank order."""
+        [world*b] int32, frames in rank order; with angles=True also angles [world*b, K, 3] fp32."""
         buf = self.buf if buf is None else buf.view(self.world, self.bytes)
-        rec = buf[:, :self.nrec * 4].contiguous().view(torch.float32).view(self.world * self.b_local, self.k, REC)
-        cnt = buf[:, self.nrec * 4:].contiguous().view(torch.int32).view(self.world * self.b_local)
-        return rec, cnt
+        n = self.world * self.b_local
+        end = (self.nrec + self.b_local) * 4
+        rec = buf[:, :self.nrec * 4].contiguous().view(torch.float32).view(n, self.k, REC)
+        cnt = buf[:, self.nrec * 4:end].contiguous().view(torch.int32).view(n)
+        if not self.nang:
+            return rec, cnt
+        return rec, cnt, buf[:, end:].contiguous().view(torch.float32).view(n, self.k, 3)
 
 
-def records_to_detections(records: np.ndarray, counts: np.ndarray, has_depth: bool) -> List[List[Detection]]:
+def records_to_detections(records: np.ndarray, counts: np.ndarray, has_depth: bool,
+                          angles: np.ndarray = None) -> List[List[Detection]]:
     """Host conversion of packed records [B, K, 10] / counts [B] into decode()'s
-    List[List[Detection]] (decode.py:206-236 field meaning)."""
+    List[List[Detection]] (decode.py:206-236 field meaning). angles [B, K, 3] (roll, pitch, yaw; NaN =
+    not decoded), when given, fills Detection.roll / .pitch / .yaw with Python floats, None where NaN."""
     out = []
     for b in range(records.shape[0]):
         dets = []
-        for r in records[b, :int(counts[b])]:
+        for i, r in enumerate(records[b, :int(counts[b])]):
             d = Detection(label=torch.tensor(int(r[0])), score=torch.tensor(r[1]), y=float(r[2]), x=float(r[3]),
                           h=float(r[4]), w=float(r[5]))
             if has_depth:
                 d.depth = float(r[6])
+            if angles is not None:
+                d.roll, d.pitch, d.yaw = (None if np.isnan(v) else float(v) for v in angles[b, i])
             dets.append(d)
         out.append(dets)
     return out
