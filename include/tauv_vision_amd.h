@@ -505,6 +505,43 @@ int tv_match_keypoints(const float* obj_records, const int32_t* obj_counts, cons
                        int32_t n_keypoints, int32_t max_slots, int32_t B, int32_t K, int32_t K_kp, int32_t* kp_det,
                        int32_t* slot_kp, int32_t* n_matched, void* stream);
 
+/* The pose stage of decode_keypoints() (decode.py:137-172, cv2.solvePnP(SOLVEPNP_ITERATIVE) there) for
+ * B x K detections in one launch, on what tv_decode (mode 1) and tv_match_keypoints leave on the device.
+ * Device pointers, async on `stream`, no workspace, no host synchronisation (graph-capturable).
+ * obj_records [B, K, 10] with obj_counts [B] and kp_records [B, K_kp, 10] with kp_counts [B] (counts
+ * clamped to [0, K] / [0, K_kp]); slot_kp [B, K, max_slots] int32 (tv_match_keypoints'); model_points
+ * [n_labels, max_slots, 3] fp32, the object's keypoints in its own frame, a NaN row = no such slot.
+ * The points of detection (b, d), d < obj_counts[b], label L = (int)obj_records[b, d, 0]: the slots s with
+ * model_points[L, s] free of NaN and k = slot_kp[b, d, s] in [0, min(kp_counts[b], K_kp)), in slot order;
+ * image point u = (double)kp[b, k, 3] * in_w, v = (double)kp[b, k, 2] * in_h (decode.py:155), object point
+ * model_points[L, s]. A label outside [0, n_labels) has no points.
+ * With n >= min_points points the pose is the (R, t) that minimises sum (fx Xc/Zc + cx - u)^2 +
+ * (fy Yc/Zc + cy - v)^2, Xc = R X + t, in double on the fp32 inputs: a linear start in the normalised
+ * coordinates ((u - cx) / fx, (v - cy) / fy) on centred and scaled object points - a homography and its
+ * decomposition when the smallest eigenvalue of the centred 3 x 3 scatter is below 1e-6 of the middle one
+ * (coplanar), the 12-parameter DLT otherwise; the sign that makes the mean depth positive; the rotation
+ * part replaced by the nearest rotation - polished by Levenberg-Marquardt on a rotation-vector increment
+ * (R <- exp([w]x) R) and t with analytic Jacobians. It ends on a step of at most 1e-12 (1 + |t|) or when no
+ * damping lowers the cost; every loop is bounded (30 Jacobi sweeps, 50 LM iterations of at most 12
+ * dampings). Only fx, fy, cx, cy of the camera are used; no distortion. A planar target has two minima:
+ * which one is returned is decided by the linear start. This is the minimiser defined here, not a
+ * restatement of OpenCV's iteration.
+ * poses [B, K, 16] fp32, every element written by every call:
+ *   0-8 R row-major, 9-11 t, 12 valid (1 / 0), 13 n (the points used), 14 RMS reprojection error in
+ *   pixels (sqrt(sum / n)), 15 LM iterations.
+ * valid = 0 - columns 0-11 and 14 NaN - when n < min_points, when a point or the start is not finite (NaN
+ * keypoints), when all object points or all pixels of the detection are equal, without convergence in 50
+ * iterations, or when a point ends at depth <= 0.
+ * Rows d >= obj_counts[b] have n = 0 and valid = 0.
+ * One wave per detection; the matrices live in LDS.
+ * TV_EINVAL before any launch: null pointers, B < 0, K outside 1..256, K_kp outside 1..1024, max_slots
+ * outside 1..32, n_labels < 1, min_points outside 6..32, non-positive in_h / in_w, fx or fy not finite or
+ * zero. B == 0 succeeds and launches nothing. */
+int tv_solve_poses(const float* obj_records, const int32_t* obj_counts, const float* kp_records,
+                   const int32_t* kp_counts, const int32_t* slot_kp, const float* model_points, int32_t n_labels,
+                   int32_t max_slots, int32_t B, int32_t K, int32_t K_kp, int32_t in_h, int32_t in_w, float fx, float fy,
+                   float cx, float cy, int32_t min_points, float* poses, void* stream);
+
 /* The detection-to-truth matching of the reference's evaluation scripts (centernet/scripts/evaluate.py:
  * 188-203, evaluate_keypoints.py:143-153) for B images in one launch, and the counts of their precision
  * and recall for T score thresholds at once. Device pointers (cols is a host array), async on `stream`,

@@ -572,6 +572,15 @@ int tv_match_keypoints(const float* obj_records, const int32_t* obj_counts, cons
                                            (hipStream_t)stream); })
 }
 
+int tv_solve_poses(const float* obj_records, const int32_t* obj_counts, const float* kp_records,
+                   const int32_t* kp_counts, const int32_t* slot_kp, const float* model_points, int32_t n_labels,
+                   int32_t max_slots, int32_t B, int32_t K, int32_t K_kp, int32_t in_h, int32_t in_w, float fx, float fy,
+                   float cx, float cy, int32_t min_points, float* poses, void* stream) {
+  TV_GUARD({ return launch_solve_poses(obj_records, obj_counts, kp_records, kp_counts, slot_kp, model_points, n_labels,
+                                       max_slots, B, K, K_kp, in_h, in_w, fx, fy, cx, cy, min_points, poses,
+                                       (hipStream_t)stream); })
+}
+
 int tv_evaluate_detections(const float* records, int32_t rec_stride, const int32_t* counts, const int32_t cols[6],
                            int32_t B, int32_t K, const uint8_t* truth_valid, const int64_t* truth_label,
                            const float* truth_center, const float* truth_size, int32_t N, int32_t mode,

@@ -479,6 +479,13 @@ int launch_match_keypoints(const float* obj_records, const int* obj_counts, cons
                            const int* kp_counts, const int* owner_label, const int* owner_slot, int n_keypoints,
                            int max_slots, int B, int K, int K_kp, int* kp_det, int* slot_kp, int* n_matched,
                            hipStream_t s);
+// Object poses from the matched keypoints (pose.hip, numerics in pose_dev.h): the contract is
+// tv_solve_poses' in include/tauv_vision_amd.h. Arguments are checked here (return 1 with the error
+// text set); B == 0 launches nothing.
+int launch_solve_poses(const float* obj_records, const int* obj_counts, const float* kp_records, const int* kp_counts,
+                       const int* slot_kp, const float* model_points, int n_labels, int max_slots, int B, int K,
+                       int K_kp, int in_h, int in_w, float fx, float fy, float cx, float cy, int min_points,
+                       float* poses, hipStream_t s);
 // Detection-to-truth matching and the precision / recall counts of the reference's evaluate scripts
 // (evaluate.hip): the contract is tv_evaluate_detections' in include/tauv_vision_amd.h. Arguments are
 // checked here (return 1 with the error text set); B * K == 0 launches nothing.

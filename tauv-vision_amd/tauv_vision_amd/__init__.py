@@ -3,13 +3,14 @@ detection path: `Centernet(DLABackbone(...), object_config)(img) -> Prediction`,
 `decode` / `decode_keypoints`, with all compute in hand-written HIP kernels
 (lib/libtauv_vision_amd.so, C ABI in include/tauv_vision_amd.h)."""
 from .config import AngleConfig, ModelConfig, ObjectConfig, ObjectConfigSet, TrainConfig  # noqa: F401
-from .centernet import (CenterpointDLA34, Centernet, CenternetDetections, CenternetDetector, Prediction,  # noqa: F401
-                        get_head_channels, initialize_weights, preprocess)
+from .centernet import (CenterpointDLA34, Centernet, CenternetDetections, CenternetDetector,  # noqa: F401
+                        CenternetPoseDetections, Prediction, get_head_channels, initialize_weights, preprocess)
 from .dla import DLABackbone  # noqa: F401
 from .decode import (Detection, DeviceAngleDecoder, DeviceDecoder, DeviceKeypointDecoder,  # noqa: F401
-                     KeypointDetection, KeypointRecords, angle_decode, angle_get_bins, angle_ranges, decode,
-                     decode_keypoints, decode_keypoints_records, decode_oriented, decode_oriented_records,
-                     decode_records, depth_decode, heatmap_detect, heatmap_nms, keypoint_detections_from_records)
+                     DevicePoseSolver, KeypointDetection, KeypointRecords, angle_decode, angle_get_bins,
+                     angle_ranges, decode, decode_keypoint_poses, decode_keypoints, decode_keypoints_records,
+                     decode_oriented, decode_oriented_records, decode_records, depth_decode, heatmap_detect,
+                     heatmap_nms, keypoint_detections_from_records, pose_model_points)
 from .yolact import (DeviceFrameMasks, FeaturePyramid, FrameMasks, Masknet, PredictionHead,  # noqa: F401
                      Resnet101Backbone, TAB10, Yolact, YolactConfig, YolactDetections, YolactDetector, YolactHead,
                      detection_records, frame_masks, pack_frame_masks, unpack_frame_masks, yolact_head_state_dict)

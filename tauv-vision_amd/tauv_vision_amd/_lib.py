@@ -142,6 +142,8 @@ EXPORTS = {
                                c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp], c_i32),
     "tv_match_keypoints": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
                             c_vp], c_i32),
+    "tv_solve_poses": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32,
+                        c_f32, c_f32, c_f32, c_i32, c_vp, c_vp], c_i32),
     "tv_evaluate_detections": ([c_vp, c_i32, c_vp, ctypes.POINTER(c_i32), c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
                                 c_i32, c_f64, c_vp, c_i32, c_vp, c_vp, c_vp], c_i32),
     "tv_train_heatmap": ([c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_vp, c_vp], c_i32),

@@ -206,24 +206,27 @@ class _NativeModel(NativeModule):
 
     def detect_keypoints(self, frames, model_config, n_detections: int = 10, keypoint_n_detections: int = 50,
                          score_threshold: float = 0.6, keypoint_score_threshold: float = 0.3, depth=None, camera=None,
-                         M_projection=None):
+                         M_projection=None, poses: bool = False, min_points: int = 6):
         """The CenterNet node's callback from the camera frames to the matched keypoints and the 3-D
         points (centernet_node.py:90-178) in one call: uint8 RGB frames [B, H, W, 3] (or [H, W, 3]) of
         any size, resized to (model_config.in_h, model_config.in_w), through a cached CenternetDetector.
         depth (uint16 millimetres, [dh, dw] or [B, dh, dw], numpy or torch) with camera = (fx, fy, cx,
         cy), or with M_projection (the node's matrix: fx, fy, cx, cy = M[0,0], M[1,1], M[0,2], M[1,2]),
         also localises every object. Returns CenternetDetections of host tensors (points None without
-        depth). One device-to-host synchronisation. The defaults are the node's (:116-117, :124)."""
+        depth). One device-to-host synchronisation. The defaults are the node's (:116-117, :124).
+        poses=True: camera (or M_projection) also gives every object with at least min_points matched
+        keypoints its pose (the node's commented-out solvePnP use, :183-191), with or without depth;
+        returns CenternetPoseDetections (the same fields, then `poses` [B, K, 16])."""
         from .localize import _host_depth
         from .yolact import _frames, _frames_on_gpu
         frames, _ = _frames(frames, None, None)
-        if camera is None and M_projection is not None and depth is not None:
+        if camera is None and M_projection is not None and (depth is not None or poses):
             import numpy as np
             M = np.asarray(M_projection, dtype=np.float64)
             if M.ndim != 2 or M.shape[0] < 2 or M.shape[1] < 3:
                 raise ValueError(f"M_projection must be at least 2 x 3, got {list(M.shape)}")
             camera = (float(M[0, 0]), float(M[1, 1]), float(M[0, 2]), float(M[1, 2]))
-        if (depth is None) != (camera is None):
+        if (depth is None) != (camera is None) and not (poses and depth is None):
             raise ValueError("depth goes with camera = (fx, fy, cx, cy) or M_projection")
         if camera is not None and len(camera) != 4:
             raise ValueError(f"camera must be (fx, fy, cx, cy), got {camera}")
@@ -234,12 +237,16 @@ class _NativeModel(NativeModule):
         dev = frames.device
         hw = (frames.shape[1], frames.shape[2])
         key = (dev.index, B, hw, int(model_config.in_h), int(model_config.in_w), int(n_detections),
-               int(keypoint_n_detections), self.precision, self._version_key())
+               int(keypoint_n_detections), self.precision, self._version_key()) + ((True,) if poses else ())
         det = getattr(self, "_detectors", {}).get(key)
         if det is None:
-            det = CenternetDetector(self, B, hw, model_config, n_detections, keypoint_n_detections, dev)
+            det = CenternetDetector(self, B, hw, model_config, n_detections, keypoint_n_detections, dev, poses=poses)
             self._detectors = {key: det}
         with torch.cuda.device(dev):
+            if poses:
+                det(frames, score_threshold, keypoint_score_threshold, None if depth is None else depth.to(dev), camera,
+                    min_points)
+                return CenternetPoseDetections(*[None if t is None else t.clone() for t in det.host()])
             det(frames, score_threshold, keypoint_score_threshold, None if depth is None else depth.to(dev), camera)
             return CenternetDetections(*[None if t is None else t.clone() for t in det.host()])
 
@@ -259,6 +266,20 @@ class CenternetDetections(NamedTuple):
     points: Optional[torch.Tensor]
 
 
+class CenternetPoseDetections(NamedTuple):
+    """CenternetDetections' fields, then `poses` [B, K, 16] fp32 (tv_solve_poses: R row-major, t, valid, n
+    points, rms reprojection error in pixels, LM iterations per object) or None without a camera."""
+    records: torch.Tensor
+    counts: torch.Tensor
+    keypoint_records: torch.Tensor
+    keypoint_counts: torch.Tensor
+    slot_kp: torch.Tensor
+    n_matched: torch.Tensor
+    kp_det: torch.Tensor
+    points: Optional[torch.Tensor]
+    poses: Optional[torch.Tensor]
+
+
 class CenternetDetector:
     """The CenterNet node's callback (centernet_node.py:90-178) for one (B, frame size) with static device
     buffers: the engine's forward into `head_out` (from the uint8 frames; frames of another size than
@@ -270,9 +291,14 @@ class CenternetDetector:
     A call launches on the current stream, allocates nothing and never synchronises, and it calls the
     engine itself (not the module's graph cache): the whole step can be captured in one graph after one
     eager call on the capture stream. `decoder`'s buffers and `points` [B, K, 8] are overwritten by every
-    call."""
+    call.
 
-    def __init__(self, model, B, frame_hw, model_config, n_detections=10, keypoint_n_detections=50, device=None):
+    poses=True: the decoder carries a `poses` section in its packed buffer and, whenever a camera is given
+    (with or without depth), tv_solve_poses runs after the matching; calls and host() return
+    CenternetPoseDetections. Still one packed copy, nothing allocated per call, capturable."""
+
+    def __init__(self, model, B, frame_hw, model_config, n_detections=10, keypoint_n_detections=50, device=None,
+                 poses=False):
         from .decode import DeviceKeypointDecoder
         from .localize import DeviceLocalizer
         if not isinstance(model, _NativeModel):
@@ -298,22 +324,32 @@ class CenternetDetector:
             torch.empty((self.B, 3) + self.size, dtype=torch.float32, device=dev)
         _, C, H, W = self.prediction.heatmap.shape
         self.K = int(n_detections)
+        self.with_poses = bool(poses)
         self.decoder = DeviceKeypointDecoder(self.B, C, oc.n_keypoints, H, W, self.K, int(keypoint_n_detections), oc,
-                                             dev)
+                                             dev, poses=self.with_poses)
+        self._posed = False
         self.localizer = DeviceLocalizer(self.B, self.K, dev)
         self.points = self.localizer.out
         self._localized = False
         self._host = None
 
-    def __call__(self, frames, score_threshold, keypoint_score_threshold, depth=None, camera=None):
+    def __call__(self, frames, score_threshold, keypoint_score_threshold, depth=None, camera=None, min_points=6):
         """frames: uint8 [B, H, W, 3] of the detector's frame size on its device — or the normalised fp32
         image [B, 3, in_h, in_w] (the fp32 entry, for frames preprocessed elsewhere). depth: uint16
         millimetres [1 or B, dh, dw] on the device, with camera = (fx, fy, cx, cy). Returns
-        CenternetDetections of the static device buffers (points None without depth)."""
-        if (depth is None) != (camera is None):
+        CenternetDetections of the static device buffers (points None without depth). A detector built
+        with poses=True also takes camera without depth and returns CenternetPoseDetections (poses None
+        without a camera); min_points: the fewest matched keypoints a pose is solved from (6..32)."""
+        if (depth is None) != (camera is None) and not (self.with_poses and depth is None):
             raise ValueError("depth and camera = (fx, fy, cx, cy) go together")
         if camera is not None and len(camera) != 4:
             raise ValueError(f"camera must be (fx, fy, cx, cy), got {camera}")
+        if self.with_poses and camera is not None:
+            import math
+            if not 6 <= int(min_points) <= 32:
+                raise ValueError(f"min_points must be in 6..32, got {min_points}")
+            if not all(math.isfinite(float(v)) for v in camera[:2]) or float(camera[0]) == 0 or float(camera[1]) == 0:
+                raise ValueError("fx and fy must be finite and not 0")
         if not isinstance(frames, torch.Tensor) or frames.device != self.device:
             raise ValueError(f"frames must be a tensor on {self.device}")
         dec = self.decoder
@@ -338,7 +374,13 @@ class CenternetDetector:
         if self._localized:
             fx, fy, cx, cy = camera
             self.localizer.boxes(res.records, res.counts, depth, fx, fy, cx, cy, 0.4, 10.0, 1.0)
-        return CenternetDetections(*res, self.points if self._localized else None)
+        if not self.with_poses:
+            return CenternetDetections(*res, self.points if self._localized else None)
+        self._posed = camera is not None
+        if self._posed:
+            dec.solve(self.model_config, camera, min_points)
+        return CenternetPoseDetections(*res, self.points if self._localized else None,
+                                       dec.poses if self._posed else None)
 
     def host(self):
         """CenternetDetections of the last call on the host: the decoder's packed buffer (and the points)
@@ -355,7 +397,11 @@ class CenternetDetector:
                 h[n:].copy_(self.points.view(-1).view(torch.uint8), non_blocking=True)
             torch.cuda.current_stream(self.device).synchronize()
         pts = h[n:].view(torch.float32).view(tuple(self.points.shape)) if self._localized else None
-        return CenternetDetections(*dec._views(h[:n]), pts)
+        if not self.with_poses:
+            return CenternetDetections(*dec._views(h[:n]), pts)
+        o = dec._offsets[-1]
+        poses = h[o:n].view(torch.float32).view(tuple(dec.poses.shape)) if self._posed else None
+        return CenternetPoseDetections(*dec._views(h[:n]), pts, poses)
 
 
 class Centernet(_NativeModel):

@@ -342,10 +342,22 @@ def decode_oriented(prediction, model_config, object_config, n_detections: int,
 
 def decode_keypoints(prediction, model_config, object_config, M_projection, n_detections: int,
                      keypoint_n_detections: int, score_threshold: float, keypoint_score_threshold: float,
-                     keypoint_angle_threshold: float) -> List[List[KeypointDetection]]:
+                     keypoint_angle_threshold: float, pose: str = "cv2") -> List[List[KeypointDetection]]:
     """decode.py:51-176: objects (no offset / ratio, depth = 1/sigmoid) and keypoints from
     the GPU; the greedy affinity-angle matching (decode.py:100-135) runs on the host over
-    at most K x K_kp records. `keypoint_angle_threshold` is unused, as in the reference."""
+    at most K x K_kp records. `keypoint_angle_threshold` is unused, as in the reference.
+    pose="cv2" (the default): the host _solve_poses, which needs OpenCV once an object has six matched
+    keypoints. pose="device": matching and poses on the device (decode_keypoint_poses: tv_match_keypoints,
+    tv_solve_poses), cam_t_object = (R float64 [3, 3], t float64 [3, 1]) for the detections whose pose is
+    valid; OpenCV is not needed and _solve_poses is not called."""
+    if pose not in ("cv2", "device"):
+        raise ValueError(f'pose must be "cv2" or "device", got {pose!r}')
+    if pose == "device":
+        rec, poses = decode_keypoint_poses(prediction, model_config, object_config, M_projection, n_detections,
+                                           keypoint_n_detections, score_threshold, keypoint_score_threshold)
+        return keypoint_detections_from_records(rec.records, rec.counts, rec.keypoint_records, rec.slot_kp,
+                                                prediction.depth is not None, model_config, object_config,
+                                                M_projection, poses=poses)
     # both decodes launched back to back, one host synchronisation
     (obj, obj_n), (kp, kp_n) = _records_many([
         (prediction.heatmap, prediction.size, None, prediction.depth, n_detections, 1,
@@ -413,6 +425,86 @@ def keypoint_owner_tables(object_config):
     return [o for o, _ in owners], [s for _, s in owners], max_slots
 
 
+POSE = 16  # R row-major (9), t (3), valid, n points, rms reprojection error in pixels, LM iterations
+
+
+def pose_model_points(object_config) -> np.ndarray:
+    """float32 [n_labels, max_slots, 3]: every object's keypoints in its own frame (ObjectConfig.keypoints),
+    NaN past an object's keypoints and for an object without keypoints: tv_solve_poses' `model_points`."""
+    _, _, S = keypoint_owner_tables(object_config)
+    out = np.full((object_config.n_labels, S, 3), np.nan, dtype=np.float32)
+    for c, cfg in enumerate(object_config.configs):
+        for s, k in enumerate(cfg.keypoints or []):
+            out[c, s] = k
+    return out
+
+
+def camera_of(M_projection):
+    """(fx, fy, cx, cy) of a projection matrix (at least 2 x 3; the node's has a zero last row)."""
+    M = np.asarray(M_projection, dtype=np.float64)
+    if M.ndim != 2 or M.shape[0] < 2 or M.shape[1] < 3:
+        raise ValueError(f"M_projection must be at least 2 x 3, got {list(M.shape)}")
+    return float(M[0, 0]), float(M[1, 1]), float(M[0, 2]), float(M[1, 2])
+
+
+class DevicePoseSolver:
+    """Static-buffer object poses from matched keypoints (tv_solve_poses, csrc/pose.hip): the reference's
+    solvePnP stage (decode.py:137-172) for every detection of a DeviceKeypointDecoder in one launch on the
+    current stream, with no allocation and no host synchronisation, so decode + match + solve can be
+    captured in one HIP graph. Holds `model_points` (pose_model_points) on the device and `poses`
+    [B, K, 16] fp32 (R row-major, t, valid, n, rms pixels, LM iterations; NaN in R, t, rms where not valid)
+    - `out`: a caller-owned contiguous buffer for it (a DeviceKeypointDecoder's `poses` section). Every
+    element is overwritten by every call. The pose is the minimiser of the pixel reprojection error
+    (include/tauv_vision_amd.h); parity with OpenCV's iteration is not claimed."""
+
+    def __init__(self, B, K, K_kp, object_config, device, out=None):
+        _lib.require_gpu()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"DevicePoseSolver needs a GPU device, got {self.device}")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if int(B) < 0 or not 1 <= int(K) <= 256 or not 1 <= int(K_kp) <= 1024:
+            raise ValueError(f"DevicePoseSolver needs B >= 0, K in 1..256 and K_kp in 1..1024, got {B}, {K}, {K_kp}")
+        self.B, self.K, self.K_kp = int(B), int(K), int(K_kp)
+        table = pose_model_points(object_config)
+        self.n_labels, self.max_slots = table.shape[:2]
+        self.model_points = torch.from_numpy(table).to(self.device)
+        self.poses = _lib.check_out(out, (self.B, self.K, POSE), self.device, "DevicePoseSolver")
+
+    def __call__(self, records, counts, keypoint_records, keypoint_counts, slot_kp, model_config, camera,
+                 min_points=6):
+        """records [B, K, 10] / counts [B], keypoint_records [B, K_kp, 10] / keypoint_counts [B], slot_kp
+        [B, K, max_slots] on the device (DeviceKeypointDecoder's), camera = (fx, fy, cx, cy). Returns the
+        device `poses`. ValueError before the launch for host tensors, other shapes or types than the
+        solver's, a camera that is not four numbers with finite non-zero fx, fy, min_points outside 6..32."""
+        from .localize import _check_camera, _check_counts, _require
+        B, K, K_kp, S = self.B, self.K, self.K_kp, self.max_slots
+        for name, t, shape in (("records", records, (B, K, REC)), ("keypoint_records", keypoint_records, (B, K_kp, REC))):
+            _require(t, name, torch.float32, self.device)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+        _check_counts(counts, B, self.device)
+        _check_counts(keypoint_counts, B, self.device)
+        _require(slot_kp, "slot_kp", torch.int32, self.device)
+        if tuple(slot_kp.shape) != (B, K, S):
+            raise ValueError(f"slot_kp must be {[B, K, S]}, got {list(slot_kp.shape)}")
+        if camera is None or len(camera) != 4:
+            raise ValueError(f"camera must be (fx, fy, cx, cy), got {camera}")
+        fx, fy, cx, cy = (float(v) for v in camera)
+        _check_camera(fx, fy)
+        if not (np.isfinite(fx) and np.isfinite(fy)):
+            raise ValueError("fx and fy must be finite")
+        if not 6 <= int(min_points) <= 32:
+            raise ValueError(f"min_points must be in 6..32, got {min_points}")
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        _lib.check(_lib.lib().tv_solve_poses(
+            vp(records), vp(counts), vp(keypoint_records), vp(keypoint_counts), vp(slot_kp), vp(self.model_points),
+            self.n_labels, S, B, K, K_kp, int(model_config.in_h), int(model_config.in_w), fx, fy, cx, cy,
+            int(min_points), vp(self.poses), _lib.stream_of(self.device)), "solve_poses")
+        return self.poses
+
+
 class DeviceKeypointDecoder:
     """Static-buffer decode_keypoints without the host: the object decode, the keypoint decode and the
     matching (tv_match_keypoints, csrc/keypoints.hip) launched on the current stream into preallocated
@@ -420,9 +512,12 @@ class DeviceKeypointDecoder:
     can be captured in one HIP graph. For a fixed (B, C labels, C_kp keypoint channels, H, W, K, K_kp)
     and object config. `records`, `counts`, `keypoint_records`, `keypoint_counts`, `slot_kp`, `n_matched`
     and `kp_det` (KeypointRecords' fields) are views of one allocation `packed`: one copy carries
-    everything. Every element is overwritten by every call."""
+    everything. Every element is overwritten by every call.
+    poses=True appends a `poses` section [B, K, 16] fp32 to `packed`, after `kp_det` (the prefix layout is
+    the same either way), which solve() fills (DevicePoseSolver, tv_solve_poses); host_poses() is its
+    host view. A call itself never touches it."""
 
-    def __init__(self, B, C, C_kp, H, W, K, K_kp, object_config, device):
+    def __init__(self, B, C, C_kp, H, W, K, K_kp, object_config, device, poses=False):
         owner_label, owner_slot, S = keypoint_owner_tables(object_config)
         if C != object_config.n_labels or C_kp != len(owner_label):
             raise ValueError(f"the object config has {object_config.n_labels} labels and {len(owner_label)} keypoints, "
@@ -443,8 +538,13 @@ class DeviceKeypointDecoder:
         self.owner_label = torch.tensor(owner_label, dtype=torch.int32).to(dev)
         self.owner_slot = torch.tensor(owner_slot, dtype=torch.int32).to(dev)
         sizes = [B * K * REC, B, B * K_kp * REC, B, B * K * S, B * K, B * K_kp]  # 4-byte elements
-        self.packed = torch.zeros(sum(sizes) * 4, dtype=torch.uint8, device=dev)
+        npose = B * K * POSE if poses else 0
+        self.packed = torch.zeros((sum(sizes) + npose) * 4, dtype=torch.uint8, device=dev)
         self._offsets = [sum(sizes[:i]) * 4 for i in range(len(sizes) + 1)]
+        self.poses = self.pose_solver = None
+        if poses:
+            self.poses = self.packed[self._offsets[-1]:].view(torch.float32).view(B, K, POSE)
+            self.pose_solver = DevicePoseSolver(B, K, K_kp, object_config, dev, out=self.poses)
         self.records, self.counts, self.keypoint_records, self.keypoint_counts, self.slot_kp, self.n_matched, \
             self.kp_det = self._views(self.packed)
         # the two decodes write straight into `packed`
@@ -501,6 +601,14 @@ class DeviceKeypointDecoder:
         return KeypointRecords(self.records, self.counts, self.keypoint_records, self.keypoint_counts, self.slot_kp,
                                self.n_matched, self.kp_det)
 
+    def solve(self, model_config, camera, min_points=6):
+        """The poses of the detections the buffers hold (one launch after match()): the device `poses`
+        [B, K, 16]. camera = (fx, fy, cx, cy). A decoder built with poses=True only."""
+        if self.pose_solver is None:
+            raise ValueError("DeviceKeypointDecoder.solve needs a decoder built with poses=True")
+        return self.pose_solver(self.records, self.counts, self.keypoint_records, self.keypoint_counts, self.slot_kp,
+                                model_config, camera, min_points)
+
     def host(self) -> KeypointRecords:
         """The last call's arrays on the host: `packed` copied to pinned memory, one synchronisation. The
         tensors are views of the decoder's pinned mirror, overwritten by the next host()."""
@@ -510,6 +618,13 @@ class DeviceKeypointDecoder:
             self._host.copy_(self.packed, non_blocking=True)
             torch.cuda.current_stream(self.device).synchronize()
         return self._views(self._host)
+
+    def host_poses(self):
+        """`poses` [B, K, 16] of the last host(): a view of the same pinned mirror (no copy, no
+        synchronisation of its own). A decoder built with poses=True, after a host()."""
+        if self.poses is None or self._host is None:
+            raise ValueError("host_poses needs a decoder built with poses=True and a host() before it")
+        return self._host[self._offsets[-1]:].view(torch.float32).view(tuple(self.poses.shape))
 
 
 _KP_DECODERS = {}  # (device, shape, owner tables) -> DeviceKeypointDecoder; under _DECODERS_LOCK
@@ -521,6 +636,24 @@ def decode_keypoints_records(prediction, model_config, object_config, n_detectio
     """decode_keypoints() with the matching on the device and without the per-detection Python objects
     (the keypoint analogue of decode_records): KeypointRecords of host numpy arrays — three launches, one
     D2H copy, one host synchronisation. The prediction must be on the GPU."""
+    return _keypoints_records(prediction, model_config, object_config, n_detections, keypoint_n_detections,
+                              score_threshold, keypoint_score_threshold, None, 6)
+
+
+def decode_keypoint_poses(prediction, model_config, object_config, M_projection, n_detections: int,
+                          keypoint_n_detections: int, score_threshold: float, keypoint_score_threshold: float,
+                          min_points: int = 6):
+    """decode_keypoints_records() plus the pose of every object with at least min_points matched
+    keypoints: (KeypointRecords of host numpy arrays, poses [B, K, 16] float32: R row-major, t, valid, n,
+    rms pixels, LM iterations). Four launches (two decodes, tv_match_keypoints, tv_solve_poses), one D2H
+    copy, one host synchronisation. M_projection: fx, fy, cx, cy = M[0,0], M[1,1], M[0,2], M[1,2]."""
+    return _keypoints_records(prediction, model_config, object_config, n_detections, keypoint_n_detections,
+                              score_threshold, keypoint_score_threshold, camera_of(M_projection), min_points)
+
+
+def _keypoints_records(prediction, model_config, object_config, n_detections, keypoint_n_detections, score_threshold,
+                       keypoint_score_threshold, camera, min_points):
+    """decode_keypoints_records (camera None) / decode_keypoint_poses through the cached decoder of the shape."""
     owner_label, owner_slot, _ = keypoint_owner_tables(object_config)
     heat = prediction.heatmap
     if not isinstance(heat, torch.Tensor) or not heat.is_cuda:
@@ -530,26 +663,37 @@ def decode_keypoints_records(prediction, model_config, object_config, n_detectio
     B, C, H, W = heat.shape
     _empty_batch_check(B)
     C_kp = prediction.keypoint_heatmap.shape[1]
+    table = None if camera is None else pose_model_points(object_config).tobytes()
     key = (heat.device.index, B, C, C_kp, H, W, int(n_detections), int(keypoint_n_detections), tuple(owner_label),
-           tuple(owner_slot))
+           tuple(owner_slot), table)
     with _DECODERS_LOCK:
         dec = _KP_DECODERS.get(key)
         if dec is None:
             if len(_KP_DECODERS) >= _DECODERS_MAX:
                 _KP_DECODERS.pop(next(iter(_KP_DECODERS)))
             dec = DeviceKeypointDecoder(B, C, C_kp, H, W, int(n_detections), int(keypoint_n_detections), object_config,
-                                        heat.device)
+                                        heat.device, poses=camera is not None)
             _KP_DECODERS[key] = dec
         with torch.cuda.device(heat.device):
             dec(prediction, model_config, score_threshold, keypoint_score_threshold)
-            return KeypointRecords(*[t.numpy().copy() for t in dec.host()])
+            if camera is None:
+                return KeypointRecords(*[t.numpy().copy() for t in dec.host()])
+            dec.solve(model_config, camera, min_points)
+            rec = KeypointRecords(*[t.numpy().copy() for t in dec.host()])
+            return rec, dec.host_poses().numpy().copy()
 
 
 def keypoint_detections_from_records(records, counts, keypoint_records, slot_kp, has_depth, model_config,
-                                     object_config, M_projection) -> List[List[KeypointDetection]]:
+                                     object_config, M_projection, poses=None) -> List[List[KeypointDetection]]:
     """The [[KeypointDetection]] of decode_keypoints() from KeypointRecords' host arrays (numpy or host
-    tensors), then the host PnP (_solve_poses) as there."""
+    tensors), then the host PnP (_solve_poses) as there. poses [B, K, 16] (tv_solve_poses' rows on the host,
+    numpy or a host tensor): cam_t_object = (R float64 [3, 3], t float64 [3, 1]) - the tuple _solve_poses
+    stores - from the valid rows instead, None elsewhere; _solve_poses is not called."""
     records, counts, keypoint_records, slot_kp = (np.asarray(a) for a in (records, counts, keypoint_records, slot_kp))
+    if poses is not None:
+        poses = np.asarray(poses)
+        if poses.shape != records.shape[:2] + (POSE,):
+            raise ValueError(f"poses must be {list(records.shape[:2]) + [POSE]}, got {list(poses.shape)}")
     out = []
     for b in range(records.shape[0]):
         dets = []
@@ -564,7 +708,11 @@ def keypoint_detections_from_records(records, counts, keypoint_records, slot_kp,
                 keypoint_scores=[None if q is None else float(q[1]) for q in kps],
                 keypoint_affinities=[None if q is None else (float(q[8]), float(q[9])) for q in kps],
                 cam_t_object=None))
-        _solve_poses(dets, model_config, object_config, M_projection)
+            if poses is not None and poses[b, d, 12] == 1:
+                row = poses[b, d].astype(np.float64)
+                dets[-1].cam_t_object = (row[0:9].reshape(3, 3), row[9:12].reshape(3, 1))
+        if poses is None:
+            _solve_poses(dets, model_config, object_config, M_projection)
         out.append(dets)
     return out
 
