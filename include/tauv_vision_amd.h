@@ -584,6 +584,75 @@ int tv_evaluate_detections(const float* records, int32_t rec_stride, const int32
                            double match_threshold, const float* score_thresholds, int32_t T, int32_t* det_truth,
                            int64_t* totals, void* stream);
 
+/* YOLACT evaluation, step 1 of 2: the pixel counts behind the mask IoU of every (detection, truth) pair of
+ * B images. Device pointers, async on `stream`, no workspace, no allocation, no host synchronisation
+ * (graph-capturable).
+ * bits [B, K, H, ceil(W / 32)] uint32 in tv_yolact_frame_masks' layout (pixel x is bit x % 32 of word
+ * x / 32), counts [B] int32 (clamped to [0, K]), seg [B, H, W] uint8, truth_valid [B, N] u8 (bool).
+ * The reference's truth is one seg map (segmentation_dataset.py:97-100, read as seg == match_index in
+ * loss.py:86), so the truth masks are disjoint:
+ *   truth t of image b owns the pixels with seg == t, provided t < N and truth_valid[b, t];
+ *   seg == 254 is invalid image (img_valid = seg != 254): such a pixel is left out of every count;
+ *   every other value is background, a value < N whose truth is not valid included.
+ * Outputs, every element written by every call:
+ *   inter [B, K, N] int32     valid pixels where bit d is set and truth t owns the pixel;
+ *   det_area [B, K] int32     valid pixels with bit d set;
+ *   truth_area [B, N] int32   pixels truth t owns.
+ * Rows d >= counts[b] are not read and give zeros, whatever the buffer holds there; bits at x >= W are not
+ * counted, whatever they hold. Two launches: the zeroing and the pass (a workgroup per image and band of 8
+ * rows, a lane per detection, popcounts into LDS, integer atomics at the end: reproducible).
+ * TV_EINVAL before any launch, with nothing written: a null pointer, B outside 1..65535, K outside 1..256,
+ * N outside 1..64, H or W < 1, W > 2^30, H * W > 2^31 - 1. */
+int tv_yolact_mask_overlap(const uint32_t* bits, const int32_t* counts, const uint8_t* seg, const uint8_t* truth_valid,
+                           int32_t B, int32_t K, int32_t N, int32_t H, int32_t W, int32_t* inter, int32_t* det_area,
+                           int32_t* truth_area, void* stream);
+
+/* YOLACT evaluation, step 2 of 2: the detection-to-truth matching behind box and mask average precision at
+ * T IoU thresholds, for B images in one launch (one workgroup per image) plus a one-thread launch that adds
+ * B to the cursor. Device pointers, async on `stream`, no allocation, no host synchronisation
+ * (graph-capturable).
+ * confidence [B, K, C + 1] fp32: the softmax rows of tv_yolact_detection_records; records [B, K, 8] of the
+ * same call, of which only the box in columns 4..7 (y, x, h, w) is read; counts [B] int32 (clamped to
+ * [0, K]); truth_valid [B, N] u8, truth_label [B, N] int64, truth_box [B, N, 4] fp32 (y, x, h, w); inter,
+ * det_area, truth_area of tv_yolact_mask_overlap; iou_thresholds [T] fp32 in any order.
+ * Rules:
+ *   - A detection's label is 1 + argmax over the foreground columns 1..C (a strict `>` scan from column 1:
+ *     the lowest index on a tie, and a NaN never replaces the running best); its score is that
+ *     probability. The background column never names a detection; records column 1 is not used (its argmax
+ *     includes the background).
+ *   - Walk order: descending score; among equal scores the lower record index first; a NaN score last.
+ *     The rank is computed from the scores: the records need not be sorted.
+ *   - Per kind (0 box, 1 mask) and threshold tau_j, independently: the detection takes the truth with the
+ *     largest IoU among the truths that are valid, still free at (kind, j), carry its label and have
+ *     IoU >= (double)tau_j; the lowest truth index wins a tie. It is then a true positive at j and the
+ *     truth is taken at j.
+ *   - Mask IoU = double(inter) / double(det_area + truth_area - inter), 0 when that union is 0.
+ *   - Box IoU in double on the fp32 values, uncontracted, in this order: corners c - s / 2 and c + s / 2;
+ *     sides min(upper) - max(lower), clamped at 0 (s > 0 ? s : 0); inter = sy * sx; a_d = h_d * w_d,
+ *     a_t = h_t * w_t; den = a_d + a_t - inter; IoU = 0 when den <= 0, else inter / den.
+ *   - A valid truth whose label is outside 1..C matches nothing and is counted in n_bad_label only.
+ * Outputs:
+ *   det_truth [B, K, 2, T] int32   the truth each record took per (kind, threshold), or -1; rows
+ *                                  k >= counts[b] are -1. Every element is written by every call.
+ *   log [capacity, K, 4] 32-bit words, 16-byte aligned: image b of the call writes row cursor[0] + b (the
+ *                                  cursor as it is when the launch runs), all K records: word 0 the score
+ *                                  (fp32), word 1 the label (int32), word 2 the tp word (uint32: bit j box
+ *                                  true positive at threshold j, bit 16 + j mask), word 3 = 1; a record
+ *                                  k >= counts[b] is four zero words. A row at or past `capacity` is not
+ *                                  written; the cursor advances all the same.
+ *   cursor [1] int64               += B, by a launch of its own behind the matching (stream-ordered).
+ *   totals [C + 2] int64           ADDED to (integer atomics): n_truth[label] for label 0..C (entry 0 stays
+ *                                  0), then n_bad_label.
+ * TV_EINVAL before any launch, with nothing written: a null pointer, B < 1, K outside 1..256, N outside
+ * 1..64, C outside 1..254, T outside 1..16, capacity < 0, a log that is not 16-byte aligned. (Any B >= 1 is
+ * taken here; tv_yolact_mask_overlap, which comes first, refuses B > 65535.) */
+int tv_yolact_evaluate_match(const float* confidence, const float* records, const int32_t* counts,
+                             const uint8_t* truth_valid, const int64_t* truth_label, const float* truth_box,
+                             const int32_t* inter, const int32_t* det_area, const int32_t* truth_area,
+                             const float* iou_thresholds, int32_t B, int32_t K, int32_t N, int32_t C, int32_t T,
+                             int64_t* cursor, int32_t* log, int64_t capacity, int32_t* det_truth, int64_t* totals,
+                             void* stream);
+
 /* Training targets of the CenterNet loss (loss.py:31-135), fp32, device pointers, async on `stream`.
  * generate_heatmap (loss.py:31-72): valid [B,n_objects] u8 (bool), label [B,n_objects] int64,
  *   center [B,n_objects,2] fp32 (y, x normalised) -> heatmap [B,n_labels,in_h/ratio,in_w/ratio]:

@@ -592,6 +592,26 @@ int tv_evaluate_detections(const float* records, int32_t rec_stride, const int32
                                                (hipStream_t)stream); })
 }
 
+int tv_yolact_mask_overlap(const uint32_t* bits, const int32_t* counts, const uint8_t* seg, const uint8_t* truth_valid,
+                           int32_t B, int32_t K, int32_t N, int32_t H, int32_t W, int32_t* inter, int32_t* det_area,
+                           int32_t* truth_area, void* stream) {
+  TV_GUARD({ return launch_yolact_mask_overlap(bits, counts, seg, truth_valid, B, K, N, H, W, inter, det_area,
+                                               truth_area, (hipStream_t)stream); })
+}
+
+int tv_yolact_evaluate_match(const float* confidence, const float* records, const int32_t* counts,
+                             const uint8_t* truth_valid, const int64_t* truth_label, const float* truth_box,
+                             const int32_t* inter, const int32_t* det_area, const int32_t* truth_area,
+                             const float* iou_thresholds, int32_t B, int32_t K, int32_t N, int32_t C, int32_t T,
+                             int64_t* cursor, int32_t* log, int64_t capacity, int32_t* det_truth, int64_t* totals,
+                             void* stream) {
+  TV_GUARD({ return launch_yolact_evaluate_match(confidence, records, counts, truth_valid,
+                                                 (const long long*)truth_label, truth_box, inter, det_area, truth_area,
+                                                 iou_thresholds, B, K, N, C, T, (long long*)cursor, log,
+                                                 (long long)capacity, det_truth, (long long*)totals,
+                                                 (hipStream_t)stream); })
+}
+
 int tv_decode_workspace_size(int32_t B, int32_t C, int32_t H, int32_t W, int32_t K, int64_t* bytes) {
   if (!bytes || B < 1 || C < 1 || H < 1 || W < 1 || K < 1) { set_error("bad argument"); return TV_EINVAL; }
   *bytes = (int64_t)decode_workspace_bytes(B, C, H, W, K);

@@ -493,6 +493,17 @@ int launch_evaluate_detections(const float* records, int rec_stride, const int* 
                                const uint8_t* truth_valid, const long long* truth_label, const float* truth_center,
                                const float* truth_size, int N, int mode, double match_threshold,
                                const float* score_thresholds, int T, int* det_truth, long long* totals, hipStream_t s);
+// YOLACT evaluation (yolact_eval.hip): the contracts are tv_yolact_mask_overlap's and
+// tv_yolact_evaluate_match's in include/tauv_vision_amd.h. Arguments are checked here (return 1 with the
+// error text set, before any launch).
+int launch_yolact_mask_overlap(const uint32_t* bits, const int* counts, const uint8_t* seg, const uint8_t* truth_valid,
+                               int B, int K, int N, int H, int W, int* inter, int* det_area, int* truth_area,
+                               hipStream_t s);
+int launch_yolact_evaluate_match(const float* confidence, const float* records, const int* counts,
+                                 const uint8_t* truth_valid, const long long* truth_label, const float* truth_box,
+                                 const int* inter, const int* det_area, const int* truth_area,
+                                 const float* iou_thresholds, int B, int K, int N, int C, int T, long long* cursor,
+                                 int* log, long long capacity, int* det_truth, long long* totals, hipStream_t s);
 int launch_uncovered_copy(const void* add, int add_ldc, void* out, int out_ldc, int C, int B,
                           int tH, int tW, int y0, int y1, int x0, int x1, int dtype,
                           hipStream_t s);

@@ -19,6 +19,8 @@ from .localize import DeviceLocalizer, localize_detections, localize_masks  # no
 from .evaluate import (DeviceEvaluator, EvaluationResult, evaluate_keypoints_precision_recall,  # noqa: F401
                        evaluate_keypoints_precision_recall_curve, evaluate_precision_recall,
                        evaluate_precision_recall_curve)
+from .yolact_evaluate import (DeviceYolactEvaluator, YolactEvaluation, average_precision,  # noqa: F401
+                              evaluate_average_precision)
 # the loss itself is tauv_vision_amd.loss.loss (`from tauv_vision_amd.loss import loss`, as the reference's
 # train.py imports it): the package attribute `loss` stays the module
 from .loss import (Angle, Losses, PoseSample, angle_in_range, angle_loss, angle_range, depth_loss,  # noqa: F401

@@ -146,6 +146,10 @@ EXPORTS = {
                         c_f32, c_f32, c_f32, c_i32, c_vp, c_vp], c_i32),
     "tv_evaluate_detections": ([c_vp, c_i32, c_vp, ctypes.POINTER(c_i32), c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
                                 c_i32, c_f64, c_vp, c_i32, c_vp, c_vp, c_vp], c_i32),
+    "tv_yolact_mask_overlap": ([c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp],
+                               c_i32),
+    "tv_yolact_evaluate_match": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
+                                  c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp], c_i32),
     "tv_train_heatmap": ([c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_vp, c_vp], c_i32),
     "tv_train_keypoint_targets": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                    c_f64, c_f64, c_vp, c_vp, c_vp, c_vp], c_i32),
