@@ -653,6 +653,48 @@ int tv_yolact_evaluate_match(const float* confidence, const float* records, cons
                              int64_t* cursor, int32_t* log, int64_t capacity, int32_t* det_truth, int64_t* totals,
                              void* stream);
 
+/* Training augmentation of B u8 camera frames in two launches: one sample of the reference's A.Compose
+ * pipelines (yolact/scripts/train.py:413-455, centernet/scripts/train.py:144-167) per frame, applied in
+ * ONE resampling, then colour, noise, blur and Normalize. Device pointers, async on `stream`, no
+ * allocation, no host synchronisation (graph-capturable). The result is a pure function of (frames, seg,
+ * records, seed): no atomics, every sum in a fixed order, so a rerun is bit-identical.
+ * frames [B, Hs, Ws, 3] uint8; seg [B, Hs, Ws] uint8 with seg_out [B, Hd, Wd] uint8 (both NULL or both
+ * given); img_out [B, 3, Hd, Wd] fp32; mean[3], std[3]: host arrays (Normalize); seed: the noise key.
+ * records [B, 32] fp32 on the device, one per frame, unused slots zero:
+ *   0-8    minv, row-major: the inverse homography, destination to source continuous coordinates (pixel
+ *          i covers [i, i + 1), centre i + 0.5)
+ *   9-11   perm: output channel c takes source channel perm[c] (clamped to 0..2)
+ *   12-14  brightness, contrast, saturation factors (1 = identity)
+ *   15     hue, a fraction of a turn;  16, 17  sat_shift, val_shift, added to HSV s and v in [0, 1]
+ *   18     noise_sigma in u8 units (0 = none);  19  blur_k in {1, 3, 5, 7} (clamped to that set)
+ * Destination pixel (b, y, x), (X, Y) = (x + 0.5, y + 0.5), everything in fp32 as written, no contraction:
+ *   w = (m6 X + m7 Y) + m8, u = ((m0 X + m1 Y) + m2) / w, v = ((m3 X + m4 Y) + m5) / w;
+ *   inside = w > 0 && 0 <= u < Ws && 0 <= v < Hs;  seg_out = inside ? seg[b, (int)v, (int)u] : 254.
+ *   Outside, the value p before the blur is 0 (the padding takes no colour and no noise). Inside: bilinear
+ *   at (u - 0.5, v - 0.5) with tv_preprocess_u8's clamped taps and blend on the u8 values (0..255, never
+ *   rounded back to u8), channels through perm; c = clamp(c brightness, 0, 255); c = clamp(contrast c +
+ *   (1 - contrast) mu_b, 0, 255), mu_b the mean over the whole source frame of gray(clamp(brightness
+ *   perm(src))), gray = (0.299 r + 0.587 g) + 0.114 b; c = clamp(saturation c + (1 - saturation) gray(c),
+ *   0, 255); if hue, sat_shift or val_shift is non-zero: RGB / 255 -> HSV, h = frac(h + hue), s and v
+ *   shifted and clamped to [0, 1], back to RGB * 255; c = clamp(c + noise_sigma n_c, 0, 255) with
+ *   Philox4x32-10 (key = seed, counter = (x, y, b, 0), outputs o0..o3), u_i = ((float)(o_i >> 8) + 0.5f)
+ *   2^-24, n_R = sqrt(-2 ln u0) cos(2 pi u1), n_G the same with sin, n_B = sqrt(-2 ln u2) cos(2 pi u3).
+ *   q = mean of p over the blur_k x blur_k window, reflect-101 at the destination border (a reflected
+ *   position is evaluated like any other, noise included; blur_k <= min(Hd, Wd) is the caller's to
+ *   ensure: further out the position is clamped); q = inside ? q : 0;
+ *   img_out[b, c, y, x] = (q / 255 - mean[c]) / std[c].
+ * workspace: tv_augment_workspace_size(B, Hs, Ws) bytes, 8-byte aligned, uninitialised: the partial sums
+ * of mu_b (one double per 4096 source pixels per frame; frames with contrast == 1 skip them).
+ * Every element of img_out and seg_out is written by every call.
+ * TV_EINVAL before any launch: null frames, records, mean, std, img_out or workspace; seg without seg_out
+ * or the reverse; B < 1 or > 65535; a non-positive size; Hs Ws 3 or Hd Wd >= 2^31; a zero std; a
+ * workspace that is too small or misaligned. */
+int tv_augment_workspace_size(int32_t B, int32_t src_h, int32_t src_w, int64_t* bytes);
+int tv_augment_frames(const uint8_t* frames, const uint8_t* seg, int32_t B, int32_t src_h, int32_t src_w,
+                      int32_t dst_h, int32_t dst_w, const float* records, uint64_t seed, const float mean[3],
+                      const float std[3], float* img_out, uint8_t* seg_out, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+
 /* Training targets of the CenterNet loss (loss.py:31-135), fp32, device pointers, async on `stream`.
  * generate_heatmap (loss.py:31-72): valid [B,n_objects] u8 (bool), label [B,n_objects] int64,
  *   center [B,n_objects,2] fp32 (y, x normalised) -> heatmap [B,n_labels,in_h/ratio,in_w/ratio]:

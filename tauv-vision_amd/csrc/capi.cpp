@@ -612,6 +612,24 @@ int tv_yolact_evaluate_match(const float* confidence, const float* records, cons
                                                  (hipStream_t)stream); })
 }
 
+int tv_augment_workspace_size(int32_t B, int32_t src_h, int32_t src_w, int64_t* bytes) {
+  TV_GUARD({
+    long long b = 0;
+    const int rc = augment_workspace_size(B, src_h, src_w, bytes ? &b : nullptr);
+    if (rc == 0) *bytes = (int64_t)b;
+    return rc;
+  })
+}
+
+int tv_augment_frames(const uint8_t* frames, const uint8_t* seg, int32_t B, int32_t src_h, int32_t src_w,
+                      int32_t dst_h, int32_t dst_w, const float* records, uint64_t seed, const float mean[3],
+                      const float std[3], float* img_out, uint8_t* seg_out, void* workspace, int64_t workspace_bytes,
+                      void* stream) {
+  TV_GUARD({ return launch_augment_frames(frames, seg, B, src_h, src_w, dst_h, dst_w, records,
+                                          (unsigned long long)seed, mean, std, img_out, seg_out, workspace,
+                                          (long long)workspace_bytes, (hipStream_t)stream); })
+}
+
 int tv_decode_workspace_size(int32_t B, int32_t C, int32_t H, int32_t W, int32_t K, int64_t* bytes) {
   if (!bytes || B < 1 || C < 1 || H < 1 || W < 1 || K < 1) { set_error("bad argument"); return TV_EINVAL; }
   *bytes = (int64_t)decode_workspace_bytes(B, C, H, W, K);

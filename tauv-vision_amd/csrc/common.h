@@ -504,6 +504,13 @@ int launch_yolact_evaluate_match(const float* confidence, const float* records, 
                                  const int* inter, const int* det_area, const int* truth_area,
                                  const float* iou_thresholds, int B, int K, int N, int C, int T, long long* cursor,
                                  int* log, long long capacity, int* det_truth, long long* totals, hipStream_t s);
+// Training augmentation (augment.hip): the contracts are tv_augment_workspace_size's and tv_augment_frames'
+// in include/tauv_vision_amd.h. Arguments are checked here (return 1 with the error text set, before any
+// launch).
+int augment_workspace_size(int B, int src_h, int src_w, long long* bytes);
+int launch_augment_frames(const uint8_t* frames, const uint8_t* seg, int B, int Hs, int Ws, int Hd, int Wd,
+                          const float* records, unsigned long long seed, const float* mean, const float* std,
+                          float* img_out, uint8_t* seg_out, void* ws, long long ws_bytes, hipStream_t s);
 int launch_uncovered_copy(const void* add, int add_ldc, void* out, int out_ldc, int C, int B,
                           int tH, int tW, int y0, int y1, int x0, int x1, int dtype,
                           hipStream_t s);

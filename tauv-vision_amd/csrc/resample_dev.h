@@ -10,16 +10,22 @@
 namespace tv {
 namespace resample {
 
-// torch's upsample_bilinear2d source index and weights, align_corners=False, scale = in / out in
-// fp32 (area_pixel_compute_source_index): src = max(0, fma(scale, d + 0.5, -0.5)), i0 = floor (never
-// past in - 1), the second tap clamped to in - 1, l1 = src - i0, l0 = 1 - l1
-__device__ __forceinline__ void lin_index(int d, int in, float scale, int& i0, int& i1, float& l0, float& l1) {
-  float src = __fmaf_rn(scale, (float)d + 0.5f, -0.5f);
+// The taps and weights of a bilinear source position `src` on an axis of `in` pixels, as torch's
+// upsample_bilinear2d clamps them (align_corners=False): src = max(0, src), i0 = floor (never past in - 1),
+// the second tap clamped to in - 1, l1 = src - i0, l0 = 1 - l1. Both taps always lie inside the frame.
+// augment.hip calls it with a homography's source position.
+__device__ __forceinline__ void lin_taps(float src, int in, int& i0, int& i1, float& l0, float& l1) {
   src = src < 0.f ? 0.f : src;
   i0 = min((int)src, in - 1);
   l1 = fminf(fmaxf(__fsub_rn(src, (float)i0), 0.f), 1.f);
   l0 = __fsub_rn(1.f, l1);
   i1 = i0 + (i0 < in - 1 ? 1 : 0);
+}
+
+// torch's upsample_bilinear2d source index and weights, align_corners=False, scale = in / out in
+// fp32 (area_pixel_compute_source_index): src = fma(scale, d + 0.5, -0.5), then lin_taps
+__device__ __forceinline__ void lin_index(int d, int in, float scale, int& i0, int& i1, float& l0, float& l1) {
+  lin_taps(__fmaf_rn(scale, (float)d + 0.5f, -0.5f), in, i0, i1, l0, l1);
 }
 
 // the blend of the four taps as torch's CPU kernel evaluates it: the row blend fma(top, h0, bottom * h1)

@@ -25,5 +25,8 @@ from .yolact_evaluate import (DeviceYolactEvaluator, YolactEvaluation, average_p
 # train.py imports it): the package attribute `loss` stays the module
 from .loss import (Angle, Losses, PoseSample, angle_in_range, angle_loss, angle_range, depth_loss,  # noqa: F401
                    focal_loss, generate_heatmap, generate_keypoint_heatmap, out_index_for_position)
+from .augment import (AugmentParams, DeviceAugmenter, SegmentationSample, augment_pose_batch,  # noqa: F401
+                      augment_segmentation_batch, identity_params, params_from_matrices, sample_centernet_params,
+                      sample_yolact_params, transform_boxes, transform_points)
 
 __version__ = "0.1.0"

@@ -150,6 +150,9 @@ EXPORTS = {
                                c_i32),
     "tv_yolact_evaluate_match": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
                                   c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp], c_i32),
+    "tv_augment_workspace_size": ([c_i32, c_i32, c_i32, ctypes.POINTER(c_i64)], c_i32),
+    "tv_augment_frames": ([c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, ctypes.c_uint64,
+                           ctypes.POINTER(c_f32), ctypes.POINTER(c_f32), c_vp, c_vp, c_vp, c_i64, c_vp], c_i32),
     "tv_train_heatmap": ([c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_vp, c_vp], c_i32),
     "tv_train_keypoint_targets": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                    c_f64, c_f64, c_vp, c_vp, c_vp, c_vp], c_i32),
