@@ -936,6 +936,20 @@ int tv_diag_convt3(const void* src, int32_t B, int32_t H, int32_t W, int32_t C, 
                    const float* bias, int32_t N, int32_t act, int32_t dtype, int32_t tile_w, int32_t tile_h, void* out,
                    int32_t out_ldc, void* stream);
 
+/* Test-only: one ConvTranspose2d(128, 128, s, stride s) + pad_to_match + skip add through convt.hip (the
+ * IDAUp / IDAUpReverse up-step), also at targets no plan reaches (larger than the up-sampled map). src:
+ * compute-dtype NHWC [B, h, w, src_ldc]; weight: host fp32 [128][128][s][s] (nn.ConvTranspose2d layout);
+ * bias: host fp32 [128]; add (the skip tensor) [B, tH, tW, add_ldc]; out [B, tH, tW, out_ldc], which may be
+ * add. Input pixel (iy, ix) writes the target pixels (iy s + py + sy, ix s + px + sx) that lie inside the
+ * target; every other pixel of out keeps its value. cus: the CU count the launch is scheduled for (0 = the
+ * device's); *np (may be null): the phases per workgroup that schedule chose, the kernel instance
+ * convt_add<T, np>. 1 <= s <= 16, sy, sx >= 0, ldc >= 128 in whole 16-byte chunks, TV_F16 / TV_BF16, else
+ * TV_EINVAL. Synchronous; allocates. */
+int tv_diag_convt_add(const void* src, int32_t B, int32_t h, int32_t w, int32_t src_ldc, const float* weight,
+                      const float* bias, int32_t s, const void* add, int32_t add_ldc, void* out, int32_t out_ldc,
+                      int32_t tH, int32_t tW, int32_t sy, int32_t sx, int32_t dtype, int32_t cus, int32_t* np,
+                      void* stream);
+
 /* Diagnostics (GPU tests): the FeaturePyramid's top-down step (feature_pyramid.py:49-50) through
  * bilinear_add, the engine's kernel for it: dst += F.interpolate(src, (dst_h, dst_w), mode="bilinear")
  * (align_corners=False: source coordinate max(0, (d + 0.5) in / out - 0.5), second tap clamped to

@@ -746,6 +746,14 @@ int tv_diag_convt3(const void* src, int32_t B, int32_t H, int32_t W, int32_t C, 
                                     (hipStream_t)stream); })
 }
 
+int tv_diag_convt_add(const void* src, int32_t B, int32_t h, int32_t w, int32_t src_ldc, const float* weight,
+                      const float* bias, int32_t s, const void* add, int32_t add_ldc, void* out, int32_t out_ldc,
+                      int32_t tH, int32_t tW, int32_t sy, int32_t sx, int32_t dtype, int32_t cus, int32_t* np,
+                      void* stream) {
+  TV_GUARD({ return tv::diag_convt_add(src, B, h, w, src_ldc, weight, bias, s, add, add_ldc, out, out_ldc, tH, tW, sy,
+                                       sx, dtype, cus, np, (hipStream_t)stream); })
+}
+
 int tv_train_heatmap(const uint8_t* valid, const int64_t* label, const float* center, int32_t B, int32_t n_objects,
                      int32_t n_labels, int32_t in_h, int32_t in_w, int32_t downsample_ratio, double sigma,
                      float* heatmap, void* stream) {

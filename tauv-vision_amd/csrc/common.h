@@ -282,6 +282,10 @@ int diag_conv_small(const void* src, int B, int H, int W, int C, int ldc, const 
 // diag.cpp: one ConvTranspose2d(3, s2, p1, op1) + bias + activation through convt3 (GPU tests)
 int diag_convt3(const void* src, int B, int H, int W, int C, int ldc, const float* weight, const float* bias, int N,
                 int act, int dtype, int tw, int tr, void* out, int out_ldc, hipStream_t s);
+// diag.cpp: one ConvTranspose2d(128, 128, s, stride s) + pad_to_match + skip add through convt.hip (GPU tests)
+int diag_convt_add(const void* src, int B, int h, int w, int src_ldc, const float* weight, const float* bias, int s,
+                   const void* add, int add_ldc, void* out, int out_ldc, int tH, int tW, int sy, int sx, int dtype,
+                   int cus, int* np, hipStream_t st);
 
 // Narrow-channel 3x3 / pad 1 conv (conv_small.hip), fp16/bf16: 16 -> 16/32 and 32 -> 32/64 input ->
 // output channels at stride 1 or 2 (DLA-34 base levels), bias + activation, NHWC

@@ -58,6 +58,15 @@ __device__ __forceinline__ uint4 gload16(const void* ptr) {
   return make_uint4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ void gstore16(void* ptr, uint4 v) { *(g_u32x4*)(ptr) = u32x4{v.x, v.y, v.z, v.w}; }
+// 8-byte accesses (whole 256-byte rows from 32 lanes)
+typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint2 gload8(const void* ptr) {
+  u32x2_t v = *(const __attribute__((address_space(1))) u32x2_t*)(ptr);
+  return make_uint2(v.x, v.y);
+}
+__device__ __forceinline__ void gstore8(void* ptr, uint2 v) {
+  *(__attribute__((address_space(1))) u32x2_t*)(ptr) = u32x2_t{v.x, v.y};
+}
 
 // ---- address spaces and raw buffer operations ------------------------------------------------
 typedef int i32x4 __attribute__((ext_vector_type(4)));

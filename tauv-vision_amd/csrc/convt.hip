@@ -9,15 +9,25 @@
 // by HBM: per input pixel and phase it reads 256 B of skip tensor and writes 256 B (the 256 B of
 // input pixel come from L2 after the first phase). The generic implicit GEMM staged that
 // through a 3-slot LDS ring and an fp32 LDS epilogue per 256-pixel tile (2.7 TB/s). Here:
-//  * a 256-thread workgroup owns one phase and a run of 32-pixel tiles; the phase's weights
-//    (128 x 128, 34 KiB with a conflict-free 272 B row pitch) move to LDS once;
-//  * each wave streams its own tiles with no barrier: the MFMA B operand (8 x 16 B of the
-//    pixel's channels per lane) and the skip chunks the epilogue adds are loaded straight
-//    into registers one tile ahead — issued before the previous tile's stores, so waiting for
-//    them never waits for those stores (vector memory completes in issue order);
-//  * the epilogue works on the accumulators in place (bias, + skip in fp32, one rounding,
-//    v_permlane32_swap into 16-byte stores), in the same arithmetic order as conv_pipe's
-//    mode-1 epilogue: (acc + bias) + skip.
+//  * a 512-thread workgroup owns one phase group and a run of 32-pixel tiles; the group's weights
+//    (128 x 128 per phase, 34 KiB with a conflict-free 272 B row pitch) move to LDS once, their
+//    rows permuted so that MFMA column n of channel fragment i is output channel 4n + i;
+//  * each wave streams its own tiles with no barrier. Pixels are the MFMA rows (the A operand,
+//    8 x 16 B of the pixel's channels per lane, straight from global memory) and the phase's
+//    weights the columns (the B operand, from LDS): accumulator register r of the four channel
+//    fragments then holds, across lanes 0-31, the 128 consecutive channels of pixel 8(r/4) + r%4
+//    and across lanes 32-63 those of the pixel four further on, 4 channels = 8 B per lane;
+//  * so every skip load and every store of a wave covers the whole 256 B of two target pixels
+//    (four whole 128 B lines) instead of 32 B of each of 32 pixels: every line is requested once,
+//    not by four instructions a quarter at a time. A lane learns the target pixel of its register
+//    from the lane that computed it (two scalar lane reads and a select). Pixels with no target
+//    (a partial tile, a cropped row or column) load pixel 0 and store past the range of the
+//    output's buffer descriptor, so no access sits behind a branch and the compiler keeps counted
+//    vmcnt waits. Skip rows are loaded one step ahead, before the previous step's stores, so
+//    waiting for them never waits for those stores (vector memory completes in issue order);
+//  * the epilogue works on the accumulators in place (bias, + skip in fp32, one rounding), in the
+//    same arithmetic order as conv_pipe's mode-1 epilogue: (acc + bias) + skip. Swapping the MFMA
+//    operand roles transposes the product and leaves each element's sum over K as it was.
 #include "conv_common.h"
 
 namespace tv {
@@ -32,6 +42,9 @@ constexpr int PW = C * WPITCH; // one phase's weights
 constexpr int NPG = 4;         // phases per workgroup on large inputs: the input tile is loaded once for all
 template <int NP>
 constexpr int lds_bytes() { return NP * (PW + C * 4); }
+// the last byte a lane reads of a phase's weights (row 3*32 + 31, lane half 1, k-step KJ - 1) is the
+// phase's own: no LDS address leaves the launch's allocation (weights, then NP * C bias floats)
+static_assert((C - 1) * WPITCH + 16 + (KJ - 1) * 32 + 16 <= PW, "weight reads stay inside the phase");
 
 template <typename T>
 __device__ __forceinline__ float lo_f(unsigned u) {
@@ -43,11 +56,13 @@ __device__ __forceinline__ float hi_f(unsigned u) {
 }
 
 struct XSet {
-  uint4 x[KJ];   // B operand: input pixel channels 16j + 8*lh .. +8
+  uint4 x[KJ];   // A operand: input pixel channels 16j + 8*lh .. +8
 };
 struct ASet {
-  uint4 a[8];    // skip / residual chunks (i, m): channels 32i + 16m + 8*lh .. +8 at the target pixel
+  uint2 a[16];   // skip / residual: channels 4*l32 .. +4 of the target of tile pixel 8(r/4) + r%4 + 4*lh
 };
+// LDS row of a phase's output channel co: MFMA column n of channel fragment i is channel 4n + i
+__device__ __forceinline__ int wrow(int co) { return ((co & 3) << 5) | (co >> 2); }
 
 // A workgroup owns NP consecutive phases of the s*s and a run of 32-pixel input tiles; per tile
 // a wave loads the input operand once and runs the NP phases, the skip chunks of the next phase
@@ -61,7 +76,7 @@ __device__ __forceinline__ void convt_tile(const ConvTParams& p, const int bx) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l32 = lane & 31, lh = lane >> 5;
-  const int group = bx / p.nchunks;
+  const int group = __builtin_amdgcn_readfirstlane(bx / p.nchunks);  // (uniform: kept in scalar registers)
   const int chunk = bx - group * p.nchunks;
   const int phase0 = group * NP;
 
@@ -84,7 +99,8 @@ __device__ __forceinline__ void convt_tile(const ConvTParams& p, const int bx) {
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
       const int i = tid + k * NT;
-      *reinterpret_cast<uint4*>(smem + (i >> 4) * WPITCH + (i & 15) * 16) = wv[k];
+      const int r = i >> 4;
+      *reinterpret_cast<uint4*>(smem + ((r & ~(C - 1)) + wrow(r & (C - 1))) * WPITCH + (i & 15) * 16) = wv[k];
     }
     if (tid < NP * C) lb[tid] = bv;
   }
@@ -95,24 +111,41 @@ __device__ __forceinline__ void convt_tile(const ConvTParams& p, const int bx) {
   const int M = p.B * hw;
   const int mt = (M + 31) / 32;
   // this wave's contiguous run of the group's tiles: an even split over all the group's waves
-  // (every CU busy: the pass is bound by each CU's own ~10 B/clk of HBM loads)
+  // (every CU busy. Measured, profiles/convt_rows: a 32-frame 120x160 up-step moves 354 MB in
+  // 0.064 ms = 5.5 TB/s, 0.88 of what a plain 16-byte-per-lane copy of the same footprint reaches
+  // on the same machine (6.26 TB/s); with 32-byte pieces of 32 lines per instruction it was 4.0)
   const long long gw = (long long)chunk * NW + wave, nw = (long long)p.nchunks * NW;
   const int t_begin = (int)(mt * gw / nw);
   const int t_end = (int)(mt * (gw + 1) / nw);
   if (t_begin >= t_end) return;
 
-  // target element offset (channel 0) of this lane's pixel in tile t for phase ph, or -1
-  auto target = [&](int t, int ph) __attribute__((always_inline)) -> long long {
+  // the output as a buffer: rows of C channels at out_ldc, the last one ending the range
+  const i32x4 orsrc = rsrc_of(p.out, (unsigned)(((size_t)(p.B * p.tH * p.tW - 1) * p.out_ldc + C) * sizeof(T)));
+  // each phase's target offset (py + sy, px + sx): uniform, kept in scalar registers
+  int oy[NP], ox[NP];
+#pragma unroll
+  for (int ph = 0; ph < NP; ++ph) {
+    const int py = __builtin_amdgcn_readfirstlane((phase0 + ph) / p.s);
+    oy[ph] = py + p.sy;
+    ox[ph] = phase0 + ph - py * p.s + p.sx;
+  }
+  // target pixel index (b, Y, X) of this lane's pixel l32 in tile t for phase ph, or -1
+  auto target = [&](int t, int ph) __attribute__((always_inline)) -> int {
     const int m = t * 32 + l32;
     if (m >= M) return -1;
-    const int phase = phase0 + ph;
-    const int py = phase / p.s, px = phase - py * p.s;
     const int b = m / hw;
     const int rem = m - b * hw;
     const int iy = rem / p.w, ix = rem - iy * p.w;
-    const int Y = iy * p.s + py + p.sy, X = ix * p.s + px + p.sx;
+    const int Y = iy * p.s + oy[ph], X = ix * p.s + ox[ph];
     if (Y >= p.tH || X >= p.tW) return -1;
-    return ((long long)(b * p.tH + Y) * p.tW + X);
+    return (b * p.tH + Y) * p.tW + X;
+  };
+  // the target of tile pixel 8(r/4) + r%4 + 4*lh, the pixel of this lane's accumulator register r,
+  // from the lane that computed it (two scalar lane reads and a select: no address registers)
+  auto target_of = [&](int tg, int r) __attribute__((always_inline)) -> int {
+    const int q = 8 * (r >> 2) + (r & 3);
+    const int t0 = __builtin_amdgcn_readlane(tg, q), t1 = __builtin_amdgcn_readlane(tg, q + 4);
+    return lh ? t1 : t0;
   };
   auto load_x = [&](int t, XSet& S) __attribute__((always_inline)) {
     const int m = t * 32 + l32;
@@ -121,20 +154,27 @@ __device__ __forceinline__ void convt_tile(const ConvTParams& p, const int bx) {
 #pragma unroll
     for (int j = 0; j < KJ; ++j) S.x[j] = gload16(src + 16 * j);
   };
+  // one instruction = the whole 256 B rows of two target pixels (phantom pixels read pixel 0)
   auto load_a = [&](int t, int ph, ASet& S) __attribute__((always_inline)) {
-    const long long tg = target(t, ph);
-    const T* add = reinterpret_cast<const T*>(p.add) + (tg < 0 ? 0 : tg) * p.add_ldc + 8 * lh;
+    const int tg = target(t, ph);
+    const char* add = reinterpret_cast<const char*>(p.add);
+    const unsigned pitch = (unsigned)p.add_ldc * (unsigned)sizeof(T);
 #pragma unroll
-    for (int q = 0; q < 8; ++q) S.a[q] = gload16(add + 16 * q);  // q = 2i + m -> channel 16q + 8lh
+    for (int r = 0; r < 16; ++r) {
+      const int tr = target_of(tg, r);
+      S.a[r] = gload8(add + ((unsigned)(tr < 0 ? 0 : tr) * pitch + 8u * l32));  // (32-bit: launch checks the extent)
+    }
   };
 
   auto compute_store = [&](int t, int ph, const XSet& X, const ASet& A) __attribute__((always_inline)) {
     const char* wl = smem + ph * PW + l32 * WPITCH + lh * 16;
-    const float* lb = reinterpret_cast<const float*>(smem + NP * PW) + ph * C;
-    const long long tg = target(t, ph);
-    T* out = reinterpret_cast<T*>(p.out) + (tg < 0 ? 0 : tg) * p.out_ldc;
-    // two halves of 64 output channels: half the accumulators live at a time (the x operand is
-    // reused, the weights are re-read from LDS) — keeps the kernel inside 256 VGPRs without spills
+    const f32x4 bb = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(smem + NP * PW) + ph * C + 4 * l32);
+    const int tg = target(t, ph);
+    const unsigned opitch = (unsigned)p.out_ldc * (unsigned)sizeof(T);
+    // two halves of two channel fragments: half the accumulators live at a time (the x operand is
+    // reused) — keeps the kernel inside 256 VGPRs without spills. The first half's result waits
+    // as packed pairs, in the registers its skip words leave free, for the second half's store.
+    unsigned o[2][16];
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
       f32x16 acc[2];
@@ -146,37 +186,19 @@ __device__ __forceinline__ void convt_tile(const ConvTParams& p, const int bx) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) wv[i] = *reinterpret_cast<const uint4*>(wl + (2 * hf + i) * 32 * WPITCH + j * 32);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) Mfma<T>::run(wv[i], X.x[j], acc[i]);
+        for (int i = 0; i < 2; ++i) Mfma<T>::run(X.x[j], wv[i], acc[i]);
         __builtin_amdgcn_sched_barrier(0);
       }
+      // register r: fragment i = channel 4*l32 + i of one pixel per lane half
 #pragma unroll
-      for (int ii = 0; ii < 2; ++ii) {
-        const int i = 2 * hf + ii;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          float v[2][4];
-#pragma unroll
-          for (int gg = 0; gg < 2; ++gg) {
-            const int G2 = 2 * m + gg;
-            const f32x4 bb = *reinterpret_cast<const f32x4*>(lb + 32 * i + 8 * G2 + 4 * lh);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[gg][e] = acc[ii][4 * G2 + e] + bb[e];
-          }
-          // registers -> 16-byte chunk: lanes 0-31 channels 32i+16m+0..7, lanes 32-63 +8..15
-          float f[8];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[0][e]), __float_as_uint(v[1][e]), false,
-                                                            false);
-            f[e] = __uint_as_float(r[0]);
-            f[4 + e] = __uint_as_float(r[1]);
-          }
-          unsigned o[4];
-          const uint4 sk = A.a[2 * i + m];
-          const unsigned sw[4] = {sk.x, sk.y, sk.z, sk.w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = pack2<T>(lo_f<T>(sw[e]) + f[2 * e], hi_f<T>(sw[e]) + f[2 * e + 1]);
-          if (tg >= 0) gstore16(out + 32 * i + 16 * m + 8 * lh, make_uint4(o[0], o[1], o[2], o[3]));
+      for (int r = 0; r < 16; ++r) {
+        const unsigned sk = hf ? A.a[r].y : A.a[r].x;
+        o[hf][r] = pack2<T>(lo_f<T>(sk) + (acc[0][r] + bb[2 * hf]), hi_f<T>(sk) + (acc[1][r] + bb[2 * hf + 1]));
+        if (hf) {
+          // (a range-checked buffer store: pixels with no target go past the range and are dropped,
+          // so no store sits behind a branch)
+          const int tr = target_of(tg, r);
+          raw_buffer_store_v2(u32x2{o[0][r], o[1][r]}, orsrc, tr < 0 ? OOB : (int)((unsigned)tr * opitch + 8u * l32), 0, 0);
         }
       }
     }
@@ -297,6 +319,13 @@ void convt_schedule(ConvTParams& p, int cu_count) {
   p.tpw = (int)((mt + chunks * convt::NW - 1) / (chunks * convt::NW));  // most tiles any wave runs
 }
 
+// the kernel addresses the skip and output rows with 32-bit byte offsets
+static bool convt_fits(const ConvTParams& p) {
+  const long long rows = (long long)p.B * p.tH * p.tW;
+  const long long ldc = std::max(p.add_ldc, p.out_ldc);
+  return rows >= 1 && rows * ldc * 2 < (1ll << 31);
+}
+
 int convt_workgroups(const ConvTParams& p) { return p.s * p.s / std::max(1, p.np) * p.nchunks; }
 
 int launch_convt_group(const ConvTParams* const* ps, int n, int dtype, hipStream_t s) {
@@ -312,6 +341,10 @@ int launch_convt_group(const ConvTParams* const* ps, int n, int dtype, hipStream
     const ConvTParams& p = *ps[k];
     if (p.tpw < 1 || p.nchunks < 1 || p.s < 1 || p.np != ps[0]->np || (p.np != 1 && p.np != NPG)) {
       set_error("convt group: unscheduled or mixed phase groups");
+      return 1;
+    }
+    if (!convt_fits(p)) {
+      set_error("convt: target tensor of 2 GiB or more");
       return 1;
     }
     wg += convt_workgroups(p);
@@ -331,6 +364,10 @@ int launch_convt(const ConvTParams& p, int dtype, hipStream_t s) {
     return 1;
   }
   using namespace convt;
+  if (!convt_fits(p)) {
+    set_error("convt: target tensor of 2 GiB or more");
+    return 1;
+  }
   if (p.np != 1 && p.np != NPG) {
     set_error("convt: bad phase group");
     return 1;

@@ -363,6 +363,52 @@ int diag_convt3(const void* src, int B, int H, int W, int C, int ldc, const floa
   return TV_OK;
 }
 
+// One ConvTranspose2d(128, 128, s, stride s) + pad_to_match + skip add through convt.hip (the engine's
+// kernel for the IDAUp / IDAUpReverse up-steps), at geometries no plan reaches (a target larger than
+// the up-sampled map): src compute dtype NHWC [B, h, w, src_ldc]; weight host fp32 [128][128][s][s]
+// (nn.ConvTranspose2d layout), bias host fp32 [128], placed as the engine's packer places them; add
+// [B, tH, tW, add_ldc]; out [B, tH, tW, out_ldc]. Input pixel (iy, ix) writes the target pixels
+// (iy s + py + sy, ix s + px + sx) inside the target; every other pixel of out is left as it was.
+// cus: the CU count the launch is scheduled for (0: the device's); *np: phases per workgroup it chose.
+int diag_convt_add(const void* src, int B, int h, int w, int src_ldc, const float* weight, const float* bias, int s,
+                   const void* add, int add_ldc, void* out, int out_ldc, int tH, int tW, int sy, int sx, int dtype,
+                   int cus, int* np, hipStream_t st) {
+  constexpr int C = 128;
+  if (!src || !weight || !bias || !add || !out || out == src || B < 1 || h < 1 || w < 1 || s < 1 || s > 16 || tH < 1 ||
+      tW < 1 || sy < 0 || sx < 0 || cus < 0 || (dtype != F16 && dtype != BF16) || src_ldc < C || add_ldc < C ||
+      out_ldc < C || !convt_supported(C, C, src_ldc, add_ldc, out_ldc)) {
+    set_error("diag_convt_add: bad argument or shape not supported by convt");
+    return TV_EINVAL;
+  }
+  const int N = s * s * C, Kpad = C;
+  std::vector<float> hw((size_t)N * Kpad, 0.f), hb(N);
+  for (int i = 0; i < s; ++i)
+    for (int j = 0; j < s; ++j)
+      for (int co = 0; co < C; ++co) {
+        const int n = (i * s + j) * C + co;
+        hb[n] = bias[co];
+        for (int ci = 0; ci < C; ++ci) hw[(size_t)n * Kpad + ci] = weight[(((size_t)ci * C + co) * s + i) * s + j];
+      }
+  DevBuf dw, db;
+  int rc = dw.upload(to_dtype(hw, dtype)), ncu = cus;
+  if (!rc) rc = db.upload(hb.data(), (size_t)N * 4);
+  if (!rc && !ncu) rc = device_cus(&ncu);
+  if (rc) return rc;
+  ConvTParams p{};
+  p.src = src; p.h = h; p.w = w; p.src_ldc = src_ldc;
+  p.weight = dw.p; p.Kpad = Kpad;
+  p.bias = (const float*)db.p;
+  p.add = add; p.add_ldc = add_ldc;
+  p.out = out; p.out_ldc = out_ldc;
+  p.B = B; p.s = s; p.tH = tH; p.tW = tW; p.sy = sy; p.sx = sx;
+  convt_schedule(p, ncu);
+  if (np) *np = p.np;
+  rc = launch_convt(p, dtype, st);
+  if (rc) return rc == TV_EHIP ? rc : TV_EINVAL;
+  TV_HIP(hipStreamSynchronize(st));  // the staging buffers are freed on return
+  return TV_OK;
+}
+
 // One narrow-channel 3x3 pad-1 conv + bias + activation through conv_small.hip (the engine's kernel
 // for DLA-34's full-resolution base levels, centerpoint_dla.py:242-246): weight host fp32
 // [N][C][3][3] placed by the engine's packer ([N][Kpad], K tap-major, channel-minor; no row padding); halo selects

@@ -170,6 +170,8 @@ EXPORTS = {
                             c_vp, c_i32, c_vp], c_i32),
     "tv_diag_convt3": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp,
                         c_i32, c_vp], c_i32),
+    "tv_diag_convt_add": ([c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32,
+                           c_i32, c_i32, c_i32, c_i32, c_vp, c_vp], c_i32),
     "tv_diag_conv1x1": ([c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp], c_i32),
     "tv_diag_conv_burst": ([c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32,
                             c_vp], c_i32),
